@@ -12,11 +12,17 @@ the N ranks itself via krcn.launch and refuses N > visible GPUs): the matrix is 
 (columns when n < d — news20 — rows otherwise) and the recurrence all-reduces
 through RCCL; total work is fixed, so scaling is "strong".
 
-Also reported: roofline of the dominant kernel (per-launch HIP-event times of
-pass 1 (X v) and pass 2 (X^T u) inside the timed region, algorithmic bytes of
-SURVEY.md §8d), the whole-HVP GB/s, a cold-cache single-HVP time, and the CPU
-baseline (the oracle's scipy restatement of loss.py:299-302, timed on this
-host on a bounded sample, rank 0 at N = 1 only).
+A plain run sets up, warms up, times the steps and prints the result line
+(HVP/s, ms_per_step, the whole-HVP GB/s from algorithmic bytes).
+`--dump-outputs DIR` also writes what the last timed step returned (alphas,
+betas, a fixed seeded sample of the basis V) as DIR/<name>.npy.
+
+`--full` adds, each from runs of its own after the timed steps: the roofline
+of the dominant kernel (per-launch HIP-event times of pass 1 (X v) and pass 2
+(X^T u), algorithmic bytes of SURVEY.md §8d), the CGS2 cost on reorth
+configurations, a cold-cache single-HVP time, warm back-to-back HVP times,
+and the CPU baseline (the oracle's scipy restatement of loss.py:299-302, timed
+on this host on a bounded sample, rank 0 at N = 1 only).
 """
 import argparse
 import json
@@ -55,6 +61,12 @@ def parse():
     p.add_argument("--partition", default="auto", choices=["auto", "rows", "cols"])
     p.add_argument("--skew", action="store_true",
                    help="skewed synthetic pattern: lognormal row lengths, power-law column popularity")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also measure the per-launch roofline, the CGS2 cost, cold and "
+                        "warm single HVPs and the CPU baseline (runs of their own; off by default)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write what the last timed step returned (alphas, betas, a seeded sample of V) "
+                        "as DIR/<name>.npy")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--rank-timeout", type=float, default=1500.0,
                    help="--gpus N: seconds after which hung ranks are killed (exit 124)")
@@ -63,7 +75,10 @@ def parse():
     p.add_argument("--placement-trials", type=int, default=None,
                    help="hot-buffer placements probed at the plan build (-1 auto = the library default, 0 off)")
     p.add_argument("--traffic-json", default=os.path.join(REPO, "profiles", "traffic.json"))
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def cpu_baseline(A, b, budget_s, label):
@@ -155,6 +170,29 @@ def flush_caches(buf):
     buf.add_(1.0)   # 512 MiB read+write evicts L2 and the 256 MiB Infinity Cache
 
 
+DUMP_V_ELEMS = 1 << 22   # whole V up to this many elements, a seeded sample of this size above it
+
+
+def dump_outputs(path, V, alphas, betas, info):
+    """What the last timed step returned, as path/<name>.npy: alphas and betas
+    whole (float64), and V (this rank's m x d basis, its own dtype) whole when
+    small, else a sample at flat positions drawn once from a fixed seed, sorted.
+    Rows >= m_eff are not part of the basis and are written as zeros."""
+    os.makedirs(path, exist_ok=True)
+    m, d = V.shape
+    if m * d <= DUMP_V_ELEMS:
+        idx = np.arange(m * d, dtype=np.int64)
+        vname = "V"
+    else:
+        idx = np.sort(np.random.default_rng(20240117).integers(0, m * d, DUMP_V_ELEMS, dtype=np.int64))
+        vname = "V_sample"
+    vals = V.view(-1)[torch.from_numpy(idx).to(V.device)].cpu().numpy()
+    vals[idx // d >= info.m_eff] = 0
+    np.save(os.path.join(path, "alphas.npy"), np.asarray(alphas, dtype=np.float64))
+    np.save(os.path.join(path, "betas.npy"), np.asarray(betas, dtype=np.float64))
+    np.save(os.path.join(path, vname + ".npy"), vals)
+
+
 def main():
     args = parse()
     if not launch.in_launched_rank():
@@ -211,14 +249,64 @@ def main():
     hvps = 0
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        _, _, _, info = step()
+        _, al, be, info = step()
         hvps += info.hvps
     torch.cuda.synchronize()
     t1 = time.perf_counter()
     problem.barrier()
     elapsed = problem.max_over_ranks(t1 - t0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, V, al, be, info)
+
+    s_val = 8 if dtype == torch.float64 else 4
+    b_hvp = synth.hvp_bytes(n, d, nnz, s_val=s_val)
+    hvp_per_s = hvps / elapsed
+    out = {
+        "metric": "Hessian-vector products/sec + achieved HBM GB/s, news20 CSR, 1/2/4/8 MI355X",
+        "value": hvp_per_s,
+        "unit": "HVP/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps,
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f64" if dtype == torch.float64 else "f32",
+        "data": (f"LIBSVM file {args.libsvm}" if args.libsvm else
+                 "synthetic (krcn.synth, shape-matched to LIBSVM " + args.config + ", seed 20240117)"),
+        "config": {"workload": f"{label}: one device Lanczos (cubic.py:77-111) of m={m} HVPs per step"
+                               + (" with CGS2 reorth" if reorth else ""),
+                   "n": n, "d": d, "nnz": nnz, "m": m, "partition": problem.partition,
+                   "parallelism": (f"{problem.partition}-sharded x{world}" if world > 1 else
+                                   f"rank 0 of {problem.partition}-sharded x{args.rehearse_shard} "
+                                   "(1-rank RCCL rehearsal)" if args.rehearse_shard > 1 else "single GPU")},
+        "achieved_hbm_gbps_hvp": b_hvp * hvp_per_s / 1e9,
+        "hvp_bytes_algorithmic": b_hvp,
+        "placement": dict(X.placement_info(),
+                          note="hot-buffer placements probed at the plan build, fastest kept "
+                               "(krcn_csr_set_placement_trials; DESIGN.md §5 Placement)"),
+    }
+    if args.full:
+        full_lines(out, args, problem, step, w, g, V, A, b, label, m, reorth, elapsed, world, rank)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    problem.close()
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def full_lines(out, args, problem, step, w, g, V, A, b, label, m, reorth, elapsed, world, rank):
+    """--full: the per-launch roofline, the CGS2 cost, cold / warm single HVPs
+    and the CPU baseline, each measured in runs of its own after the timed
+    steps, added to the result line `out`."""
+    X = problem.X
+    dtype = V.dtype
+    dev = V.device
+    n, d = A.shape
+    nnz = A.nnz
     # per-pass HIP-event times on the library's stream, in separate steps so the
-    # events do not perturb the headline number above
+    # events do not perturb the headline number
     X.prof_enable(True)
     for _ in range(max(1, min(args.steps, 5))):
         step()
@@ -317,45 +405,18 @@ def main():
                        "achieved_gbps": rbytes / (reorth_ms * 1e-3) / 1e9 if reorth_ms > 0 else None,
                        "method": "step time minus the same Lanczos without reorth, same handle"}
 
-    hvp_per_s = hvps / elapsed
-    out = {
-        "metric": "Hessian-vector products/sec + achieved HBM GB/s, news20 CSR, 1/2/4/8 MI355X",
-        "value": hvp_per_s,
-        "unit": "HVP/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": 1e3 * elapsed / args.steps,
-        "higher_is_better": True,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": "f64" if dtype == torch.float64 else "f32",
-        "data": (f"LIBSVM file {args.libsvm}" if args.libsvm else
-                 "synthetic (krcn.synth, shape-matched to LIBSVM " + args.config + ", seed 20240117)"),
-        "config": {"workload": f"{label}: one device Lanczos (cubic.py:77-111) of m={m} HVPs per step"
-                               + (" with CGS2 reorth" if reorth else ""),
-                   "n": n, "d": d, "nnz": nnz, "m": m, "partition": problem.partition,
-                   "parallelism": (f"{problem.partition}-sharded x{world}" if world > 1 else
-                                   f"rank 0 of {problem.partition}-sharded x{args.rehearse_shard} "
-                                   "(1-rank RCCL rehearsal)" if args.rehearse_shard > 1 else "single GPU")},
-        "achieved_hbm_gbps_hvp": b_hvp * hvp_per_s / 1e9,
-        "hvp_bytes_algorithmic": b_hvp,
-        "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBPS,
-                     "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic,
-                     "algorithmic_bytes_per_launch": dom_bytes, "avg_launch_us": dom_us,
-                     "launches": {k: {"avg_us": round(v[0], 3), "algorithmic_bytes": v[1],
-                                      "achieved_gbps": round(v[1] / (v[0] * 1e-6) / 1e9, 1) if v[0] > 0 else None}
-                                  for k, v in launches.items()},
-                     "pass1_with_combine_us": p1_us, "pass2_us": p2_us, "launches_timed": prof["count"],
-                     "fused_step_b": fused, "fused_xt": xt, "formats": fmt,
-                     "plan": {"pass1": list(plan["pass1"]), "pass2": list(plan["pass2"]),
-                              "fields": "(slices, <0: sorted tiles), lanes, tiles, grid"},
-                     "traffic_source": traffic_src},
-        "placement": dict(X.placement_info(),
-                          note="hot-buffer placements probed at the plan build, fastest kept "
-                               "(krcn_csr_set_placement_trials; DESIGN.md §5 Placement)"),
-        "cpu_baseline": None,
-    }
+    out["roofline"] = {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBPS,
+                       "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic,
+                       "algorithmic_bytes_per_launch": dom_bytes, "avg_launch_us": dom_us,
+                       "launches": {k: {"avg_us": round(v[0], 3), "algorithmic_bytes": v[1],
+                                        "achieved_gbps": round(v[1] / (v[0] * 1e-6) / 1e9, 1) if v[0] > 0 else None}
+                                    for k, v in launches.items()},
+                       "pass1_with_combine_us": p1_us, "pass2_us": p2_us, "launches_timed": prof["count"],
+                       "fused_step_b": fused, "fused_xt": xt, "formats": fmt,
+                       "plan": {"pass1": list(plan["pass1"]), "pass2": list(plan["pass2"]),
+                                "fields": "(slices, <0: sorted tiles), lanes, tiles, grid"},
+                       "traffic_source": traffic_src}
+    out["cpu_baseline"] = None
     if reorth_info is not None:
         out["reorth"] = reorth_info
     solo = world == 1 and args.rehearse_shard <= 1   # whole-problem single-GPU lines
@@ -420,11 +481,6 @@ def main():
                                         "events": "torch.cuda.Event pair around each HVP (rounds 1-4)"}
     if rank == 0 and solo and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(A, b, args.cpu_seconds, label)
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    problem.close()
-    if world > 1:
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

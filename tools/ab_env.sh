@@ -9,7 +9,7 @@ vals=(); while [ $# -gt 0 ] && [ "$1" != "--" ]; do vals+=("$1"); shift; done
 [ "$1" == "--" ] && shift
 for i in $(seq 1 $reps); do
   for v in "${vals[@]}"; do
-    env "$var=$v" timeout -k 10 180 python3 $R/bench.py --steps 10 --warmup 5 --no-cpu-baseline --no-cold "$@" > /tmp/ab_env.log 2>&1 || { echo "FAIL $var=$v"; tail -5 /tmp/ab_env.log; exit 1; }
+    env "$var=$v" timeout -k 10 180 python3 $R/bench.py --full --steps 10 --warmup 5 --no-cpu-baseline --no-cold "$@" > /tmp/ab_env.log 2>&1 || { echo "FAIL $var=$v"; tail -5 /tmp/ab_env.log; exit 1; }
     python3 $R/tools/ab_line.py "$var=$v" /tmp/ab_env.log
   done
 done

@@ -27,7 +27,9 @@ def main():
         subprocess.run([sys.executable, os.path.join(REPO, "tools", "prof_summary.py"), prof, f"{tag}_{cfg}", k],
                        check=True, stdout=subprocess.DEVNULL)
         ent = json.load(open(os.path.join(REPO, "profiles", "traffic.json")))[k]
-        line = [x for x in open(os.path.join(REPO, "gpurun_out", f"{tag}_bench_{cfg}.json")) if x.startswith("{")][-1]
+        # the `bench.py --full` line tools/prof_all.sh left under $BENCH_OUT (default bench_out/)
+        bench_out = os.environ.get("BENCH_OUT") or os.path.join(REPO, "bench_out")
+        line = [x for x in open(os.path.join(bench_out, f"{tag}_bench_{cfg}.json")) if x.startswith("{")][-1]
         d = json.loads(line)
         r = d["roofline"]
         dom = max(r["launches"], key=lambda k: r["launches"][k]["avg_us"])

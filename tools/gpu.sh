@@ -51,7 +51,7 @@ run_step() {
     profr)   # profr:<tag>:<cfg>:<N>: rehearsal line (rank 0 of N) + its rocprofv3 stats / FETCH / WRITE
       local cfg=${a[2]} nr=${a[3]}
       local bt=${tag}_rehearse${nr}_$cfg   # (not ${tag}_bench_$cfg: a bench step of the same tag keeps its line)
-      timeout -k 10 400 python3 bench.py --config $cfg --rehearse-shard $nr --steps 10 --warmup 3 \
+      timeout -k 10 400 python3 bench.py --full --config $cfg --rehearse-shard $nr --steps 10 --warmup 3 \
         > gpurun_out/$bt.log 2>&1 || { tail -8 gpurun_out/$bt.log; return 1; }
       grep '"metric"' gpurun_out/$bt.log > gpurun_out/$bt.json
       python3 tools/ab_line.py "$cfg rank of $nr" gpurun_out/$bt.json
@@ -59,7 +59,7 @@ run_step() {
     procs)
       local n=${a[2]} cfg=${a[3]:-news20}
       for i in $(seq 1 $n); do
-        timeout -k 10 200 python3 bench.py --config $cfg --no-cpu-baseline --no-cold --steps 10 \
+        timeout -k 10 200 python3 bench.py --full --config $cfg --no-cpu-baseline --no-cold --steps 10 \
           > gpurun_out/${tag}_p$i.log 2>&1 || { tail -5 gpurun_out/${tag}_p$i.log; return 1; }
         python3 tools/ab_line.py "proc $i" gpurun_out/${tag}_p$i.log
       done ;;
@@ -67,7 +67,7 @@ run_step() {
       local reps=${a[2]} la=${a[3]} lb=${a[4]}
       for i in $(seq 1 $reps); do
         for lib in "$la" "$lb"; do
-          KRCN_LIB=$R/$lib timeout -k 10 200 python3 bench.py --steps 10 --warmup 5 --no-cpu-baseline --no-cold \
+          KRCN_LIB=$R/$lib timeout -k 10 200 python3 bench.py --full --steps 10 --warmup 5 --no-cpu-baseline --no-cold \
             $(sp "${a[5]}") > /tmp/ab.log 2>&1 || { echo "FAIL $lib"; tail -5 /tmp/ab.log; return 1; }
           python3 tools/ab_line.py "$lib" /tmp/ab.log
         done
