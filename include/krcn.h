@@ -23,7 +23,13 @@
  *     communicator, the plan queries, or the first compute call of any other
  *     handle), in krcn_csr_reserve(.., reorth = 1) (CGS2 workspace) and in the
  *     first krcn_cg_solve.  krcn_lanczos allocates nothing on a handle that is
- *     reserved for its m; a handle of a multi-rank communicator never builds
+ *     reserved for its m.  The coordinate calls (krcn_coord_*) allocate their
+ *     own workspace at the first of them and grow it when k grows: the device
+ *     cols and delta (k_cap int32 + k_cap doubles) and a k_cap x k_cap fp64
+ *     result, cap (12 + 8 cap) device bytes for k_cap = k rounded up to a
+ *     multiple of 64, counted by krcn_csr_owned_bytes and freed by
+ *     krcn_csr_destroy, plus pinned host memory (the result's mirror and the
+ *     staging ring).  A handle of a multi-rank communicator never builds
  *     or allocates inside a compute call (that call fails instead), so no
  *     rank synchronises the device while its peers wait in a collective.
  *   - Errors: every call returns a krcn_status (0 = OK).  The message of the
@@ -246,6 +252,53 @@ krcn_status krcn_loss_mean(krcn_csr* h, const void* Ax, const void* b,
  * optimizer.py:164-166), over iterates kept on the device. */
 krcn_status krcn_loss_values(krcn_csr* h, int k, const void* const* xs_host, const void* b,
                              double* out_host, void* stream);
+
+/* ---- coordinate blocks (SSCN) --------------------------------------------- */
+/* A selection is k column indices cols_host (HOST int32): any order, repeats
+ * allowed, 1 <= k <= KRCN_COORD_MAX.  It is validated on the host before
+ * anything is launched: an index outside [0, d) or a k outside the range is
+ * KRCN_ERR_INVALID with the offending position in the error string; no bad
+ * index reaches a kernel.  Unsharded handles only (a sharded handle gets
+ * KRCN_ERR_UNSUPPORTED), both dtypes: device vectors have the handle's dtype,
+ * sums are accumulated in fp64 in a fixed order, host outputs are double.
+ * The calls read the handle's transposed CSR (every column of X a row-sorted
+ * list with distinct rows: a CSR without repeated entries), need no pass
+ * plans (they never trigger the plan build) and use their own workspace, not
+ * the handle's scratch vectors.  n == 0 or nnz == 0: l2 x_I, l2 I and a copy
+ * of Ax_in (zeros if it is NULL), without reading the matrix.
+ * Staging: cols_host and delta_host may be overwritten as soon as a call
+ * returns.  Each call copies them into the next slot of a ring of pinned
+ * staging slots (a host memcpy before the call returns) and enqueues the H2D
+ * copy from that slot with an event behind it; a slot is refilled only once
+ * its event has completed, so back-to-back asynchronous calls never share a
+ * slot in flight, and the one device copy is ordered by the handle's stream. */
+enum { KRCN_COORD_MAX = 1024 };
+/* SYNCHRONOUS. g_host[a] = sum_r X[r,c_a] (expit(Ax_r) - b_r) / n_global (+ l2 x[c_a] when l2 != 0);
+ * entry a depends on column c_a alone, not on the rest of the selection.
+ * Replaces LogisticRegression.partial_gradient, loss.py:234-247. */
+krcn_status krcn_coord_gradient(krcn_csr* h, int k, const int32_t* cols_host, const void* Ax,
+                                const void* b, const void* x, double l2, double* g_host, void* stream);
+/* SYNCHRONOUS. H_host[a*k+b] = sum_r w_r X[r,c_a] X[r,c_b] / n_global + l2 [a == b],
+ * w_r = s(1-s), s = expit(Ax_r), computed in the kernel with krcn_weights' arithmetic.
+ * H_host is exactly symmetric, and positions that repeat an index carry the
+ * same sums (the kernel runs on the distinct columns; l2 sits on a == b only,
+ * as the reference's l2 * eye(k)).  Replaces partial_hessian, loss.py:257-264;
+ * with cols = 0..d-1 also hessian, loss.py:249-255. */
+krcn_status krcn_coord_hessian(krcn_csr* h, int k, const int32_t* cols_host, const void* Ax,
+                               double l2, double* H_host, void* stream);
+/* Asynchronous. Ax_out = Ax_in + X[:, cols] delta (Ax_in may be NULL: Ax_out = X[:, cols] delta;
+ * Ax_out may alias Ax_in), summed per row column by column in the order of
+ * cols, repeats included, product and sum rounded separately: scipy's
+ * csc_matvec order, so fp64 is bitwise Ax_in + A.tocsc()[:, cols] @ delta.
+ * Replaces update_mat_vec_product, loss.py:279-281. */
+krcn_status krcn_coord_update(krcn_csr* h, int k, const int32_t* cols_host, const double* delta_host,
+                              const void* Ax_in, void* Ax_out, void* stream);
+/* Rows of the LDS window the coordinate kernels walk the samples in: 0 = auto
+ * (Hessian: what fits the LDS, 20,416 rows per block; update: 256 rows per
+ * wave), otherwise a multiple of 64, clamped to 20,416 (Hessian) and 1,024
+ * (update); tests use small values to cross window boundaries on small n.
+ * Results of the update do not depend on it. */
+krcn_status krcn_csr_set_coord_window(krcn_csr* h, int rows);
 
 /* ---- Lanczos (optimizer/cubic.py:77-111) -------------------------------- */
 /* SYNCHRONOUS on return of alphas/betas/info.  Runs the reference three-term

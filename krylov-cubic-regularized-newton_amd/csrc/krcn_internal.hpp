@@ -3,6 +3,7 @@
 // The library is split into translation units that compile in parallel:
 //   krcn_plan.hip        handle lifecycle, transposed CSR, pass plans, comm, profiling
 //   krcn_ops.hip         objective pieces (Ax, X^T u, weights, HVP, gradient, loss, dots)
+//   krcn_coord.hip       coordinate blocks of SSCN (gradient, Hessian block, Ax update)
 //   krcn_lanczos_f64.hip / krcn_lanczos_f32.hip
 //                        the device Lanczos recurrence (krcn_lanczos_impl.hpp), one dtype each
 // This header holds the handle layout, the error macros and the pass launcher
@@ -188,6 +189,8 @@ struct PassPlan {
   int64_t pcap = 0;           // entries of the handle's partials buffers (ensure_plans)
 };
 
+struct CoordWs;   // krcn_coord.hip: the workspace of the coordinate calls
+
 struct krcn_csr {
   int device = 0, dtype = KRCN_F64, shard = KRCN_SHARD_NONE;
   size_t vs = 8;
@@ -237,6 +240,8 @@ struct krcn_csr {
   int reorth_m = 0;           // CGS2 workspace reserved for Lanczos m <= this (krcn_csr_reserve)
   void* cg_r = nullptr;       // CG vectors r | p | q (3 d-vectors, krcn_cg_solve)
   struct krcn::CgState* cg_st = nullptr;
+  CoordWs* cw = nullptr;      // coordinate workspace (first krcn_coord_* call; its device bytes are in owned)
+  int coord_window = 0;       // krcn_csr_set_coord_window (0: auto)
   size_t owned = 0;
   krcn_comm* comm = nullptr;
   bool prof = false;
@@ -273,6 +278,7 @@ struct krcn_csr {
 };
 
 void free_plan(PassPlan& P);
+void coord_free(krcn_csr* h);   // krcn_coord.hip: releases h->cw
 krcn_status ensure_plans(krcn_csr* h);
 // `reps` back-to-back local HVPs (pass 1 and pass 2 of the handle's plans, no
 // collective) on the handle's scratch vectors: *us = microseconds per HVP

@@ -84,6 +84,7 @@ static krcn_status destroy_impl(krcn_csr* h) {
                   h->fcnt};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
+  coord_free(h);
   if (h->hostbuf) (void)hipHostFree(h->hostbuf);
   if (h->hostres) (void)hipHostFree(h->hostres);
   if (h->gexec) (void)hipGraphExecDestroy(h->gexec);

@@ -25,6 +25,7 @@ KRCN_SLICING_AUTO, KRCN_SLICING_OFF = 0, 1
 KRCN_FORMAT_AUTO, KRCN_FORMAT_WAVE, KRCN_FORMAT_SORTED, KRCN_FORMAT_WINDOW, KRCN_FORMAT_JAG = 0, 1, 2, 3, 4
 KRCN_PLAN_WAVE, KRCN_PLAN_SORTED, KRCN_PLAN_WINDOW_SLICES, KRCN_PLAN_WINDOW_ACCUM = 1, 2, 3, 4
 KRCN_SPACE_N, KRCN_SPACE_D = 0, 1
+KRCN_COORD_MAX = 1024
 
 _STATUS_NAMES = {1: "KRCN_ERR_INVALID", 2: "KRCN_ERR_HIP", 3: "KRCN_ERR_RCCL",
                  4: "KRCN_ERR_UNSUPPORTED"}
@@ -81,6 +82,10 @@ SIGNATURES = {
     "krcn_gradient": [_vp, _vp, _vp, _vp, _d, _vp, _vp],
     "krcn_loss_mean": [_vp, _vp, _vp, _dp, _vp],
     "krcn_loss_values": [_vp, _i, ctypes.POINTER(_vp), _vp, _dp, _vp],
+    "krcn_coord_gradient": [_vp, _i, _vp, _vp, _vp, _vp, _d, _dp, _vp],
+    "krcn_coord_hessian": [_vp, _i, _vp, _vp, _d, _dp, _vp],
+    "krcn_coord_update": [_vp, _i, _vp, _dp, _vp, _vp, _vp],
+    "krcn_csr_set_coord_window": [_vp, _i],
     "krcn_lanczos": [_vp, _vp, _vp, _i, _i, _d, _d, _vp, _dp, _dp,
                      ctypes.POINTER(LanczosInfo), _vp],
     "krcn_basis_combine": [_vp, _i, _vp, _dp, _vp, _vp, _vp],

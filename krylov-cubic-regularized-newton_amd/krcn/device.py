@@ -260,6 +260,54 @@ class DeviceCSR:
              _stream(self.device))
         return [float(v) for v in out[:k]]
 
+    # -- coordinate blocks (SSCN) -------------------------------------------
+    @staticmethod
+    def _selection(cols):
+        c = np.ascontiguousarray(np.asarray(cols).reshape(-1), dtype=np.int32)
+        if not np.array_equal(c, np.asarray(cols).reshape(-1)):
+            raise ValueError("cols must be integers that fit int32")
+        return c, c.ctypes.data_as(ctypes.c_void_p)
+
+    def set_coord_window(self, rows=0):
+        """Rows of the LDS window of the coordinate kernels: 0 auto, else a multiple of 64."""
+        call("krcn_csr_set_coord_window", self._h, int(rows))
+
+    def coord_gradient(self, cols, Ax, b, x=None, l2=0.0):
+        """Coordinates `cols` of the gradient (loss.py:234-247): numpy float64 (k,)."""
+        c, cp = self._selection(cols)
+        self._check(Ax, self.n, "Ax")
+        self._check(b, self.n, "b")
+        if l2 != 0.0:
+            self._check(x, self.d, "x")
+        g = np.zeros(max(len(c), 1), dtype=np.float64)
+        call("krcn_coord_gradient", self._h, len(c), cp, _ptr(Ax), _ptr(b), _ptr(x), float(l2),
+             g.ctypes.data_as(_lib._dp), _stream(self.device))
+        return g[:len(c)]
+
+    def coord_hessian(self, cols, Ax, l2=0.0):
+        """The cols x cols block of the Hessian (loss.py:257-264): numpy float64 (k, k)."""
+        c, cp = self._selection(cols)
+        self._check(Ax, self.n, "Ax")
+        k = len(c)
+        H = np.zeros((max(k, 1), max(k, 1)), dtype=np.float64)
+        call("krcn_coord_hessian", self._h, k, cp, _ptr(Ax), float(l2), H.ctypes.data_as(_lib._dp),
+             _stream(self.device))
+        return H[:k, :k]
+
+    def coord_update(self, cols, delta, Ax=None, out=None):
+        """Ax + X[:, cols] delta (loss.py:279-281; X[:, cols] delta when Ax is None);
+        out may be Ax.  Asynchronous: cols and delta may be reused at once."""
+        c, cp = self._selection(cols)
+        dl = np.ascontiguousarray(np.asarray(delta).reshape(-1), dtype=np.float64)
+        if len(dl) != len(c):
+            raise ValueError(f"delta must have one entry per column ({len(c)}), got {len(dl)}")
+        if Ax is not None:
+            self._check(Ax, self.n, "Ax")
+        out = self.empty_n() if out is None else self._check(out, self.n, "out")
+        call("krcn_coord_update", self._h, len(c), cp, dl.ctypes.data_as(_lib._dp), _ptr(Ax), _ptr(out),
+             _stream(self.device))
+        return out
+
     # -- Lanczos -----------------------------------------------------------
     def lanczos(self, w, g, m, reorth=False, tol=1e-6, l2=0.0, V=None):
         """Three-term Lanczos on v -> hvp(w, v) from g (cubic.py:77-111).

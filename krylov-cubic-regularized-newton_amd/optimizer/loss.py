@@ -356,44 +356,42 @@ class LogisticRegression(Oracle):
             raise NotImplementedError(f"{what} is implemented for unsharded problems")
 
     def hessian(self, x):
-        """Dense Hessian X^T diag(w) X / n + l2 I (loss.py:249-255), one device
-        HVP per column; numpy (d, d), for the full-space CRN at small d."""
+        """Dense Hessian X^T diag(w) X / n + l2 I (loss.py:249-255): the
+        coordinate-block kernel over all columns for d <= KRCN_COORD_MAX, one
+        device HVP per column above that; numpy (d, d), for the full-space CRN
+        at small d."""
+        self._no_shards("the dense / coordinate Hessian")
+        if self.dim <= _lib.KRCN_COORD_MAX:
+            return self.device_matrix.coord_hessian(np.arange(self.dim), self._device_Ax(x), float(self.l2))
         cols = self._unit_columns(x, range(self.dim))
         return torch.stack(cols, dim=1).cpu().numpy().astype(np.float64)
 
     def partial_gradient(self, x, I):
-        """Coordinates I of the gradient (loss.py:234-247): the device gradient
-        (per-coordinate sums in row order, X^T of loss.py:239) gathered at I;
-        numpy (len(I),)."""
+        """Coordinates I of the gradient (loss.py:234-247) by the coordinate
+        kernel, which reads the columns I of X alone; numpy (len(I),)."""
         self._no_shards("partial_gradient")
-        g = self.gradient(self.to_device(x))
-        idx = torch.from_numpy(np.asarray(I, dtype=np.int64)).to(self.device)
-        return g.index_select(0, idx).cpu().numpy().astype(np.float64)
+        Ax = self._device_Ax(x)
+        xd = self.to_device(x) if self.l2 != 0 else None
+        return self.device_matrix.coord_gradient(I, Ax, self._b_dev, xd, float(self.l2))
 
     def partial_hessian(self, x, I):
-        """The I x I block of the Hessian (loss.py:257-264): len(I) device HVPs
-        on unit vectors, rows I kept; a scipy sparse (CSR) matrix like the
-        reference's A_weighted @ A[:, I] / n + l2 eye."""
+        """The I x I block of the Hessian (loss.py:257-264) by the coordinate
+        kernel; a scipy sparse (CSR) matrix like the reference's
+        A_weighted @ A[:, I] / n + l2 eye."""
         import scipy.sparse as sp
-        idx = torch.from_numpy(np.asarray(I, dtype=np.int64)).to(self.device)
-        cols = [c.index_select(0, idx) for c in self._unit_columns(x, I)]
-        return sp.csr_matrix(torch.stack(cols, dim=1).cpu().numpy().astype(np.float64))
+        self._no_shards("partial_hessian")
+        return sp.csr_matrix(self.device_matrix.coord_hessian(I, self._device_Ax(x), float(self.l2)))
 
     def update_mat_vec_product(self, Ax, delta, I):
         """Ax + A[:, I] delta becomes the cached product, reused for every x
-        until reset() (loss.py:279-281, SSCN's incremental update): one device
-        pass over X with delta scattered into a zero d-vector."""
+        until reset() (loss.py:279-281, SSCN's incremental update), by the
+        coordinate kernel in scipy's csc_matvec order."""
         self._no_shards("update_mat_vec_product")
-        from krcn.vec import VecContext
-        dv = torch.zeros(self.dim, dtype=self.dtype, device=self.device)
-        idx = torch.from_numpy(np.asarray(I, dtype=np.int64)).to(self.device)
-        dv[idx] = torch.from_numpy(np.asarray(delta, dtype=np.float64)).to(self.device, self.dtype)
-        AI = self.device_matrix.matvec(dv)
         # the reference starts the cache as zeros(n) (loss.py:283-286): with
         # store_mat_vec_prod=False SSCN hands back that never-written zero
         # vector (here: None) and the sum is never read (mat_vec_product
         # recomputes A x), so A[:, I] delta alone stands in for it
-        self._mat_vec_prod = AI if Ax is None else VecContext.for_device(self.device).axpy(1.0, AI, Ax)
+        self._mat_vec_prod = self.device_matrix.coord_update(I, delta, Ax)
         self._w = None
         self.reuse = True
 
