@@ -146,7 +146,7 @@ krcn_status krcn_csr_create(int device, int64_t n, int64_t d, int64_t nnz,
                             const void* data, int dtype, int64_t n_global,
                             int shard_mode, krcn_csr** out);
 krcn_status krcn_csr_destroy(krcn_csr* h);
-/* Device bytes owned by the handle (transpose + workspace). */
+/* Device bytes the handle holds now (transpose, pass plans, workspace). */
 krcn_status krcn_csr_owned_bytes(const krcn_csr* h, int64_t* bytes_host);
 /* Row-group policy for X (pass 1) and X^T (pass 2): KRCN_LANES_AUTO,
  * KRCN_LANES_SEQUENTIAL, or an explicit power of two 2..64. */

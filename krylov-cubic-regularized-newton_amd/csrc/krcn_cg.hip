@@ -10,9 +10,7 @@ constexpr int kCgCheckEvery = 16;   // iterations between host reads of the done
 
 krcn_status ensure_cg_ws(krcn_csr* h) {
   if (h->cg_r) return KRCN_OK;
-  char* p = nullptr;
-  CHK(dalloc(h, &p, size_t(3) * size_t(h->d) * h->vs));
-  h->cg_r = p;
+  CHK(h->own.alloc(&h->cg_r, std::max<size_t>(size_t(3) * size_t(h->d) * h->vs, 1)));
   CHK(dalloc(h, &h->cg_st, 1));
   return KRCN_OK;
 }

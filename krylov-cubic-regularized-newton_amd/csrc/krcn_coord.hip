@@ -13,7 +13,7 @@ using namespace krcn;
 // The coordinate workspace for selections of up to cap columns (cap = k rounded
 // up to a multiple of 64; grown when k grows).
 //   device  delta (cap doubles) | cols (cap int32) | result (cap x cap doubles)
-//           = cap (12 + 8 cap) bytes, accounted in h->owned
+//           = cap (12 + 8 cap) bytes, one block of the handle's owner table
 //   pinned  the result's host mirror | kCoordSlots staging slots (delta | cols)
 // Staging: a call copies cols_host / delta_host into the next slot of the ring
 // (a host memcpy, so the caller may overwrite its arrays once the call
@@ -34,7 +34,6 @@ struct CoordWs {
   hipEvent_t ev[kCoordSlots] = {};
   bool busy[kCoordSlots] = {};
   int next = 0;
-  size_t dev_bytes = 0;
 };
 
 static size_t coord_slot_bytes(int cap) { return size_t(cap) * 12; }
@@ -42,10 +41,7 @@ static size_t coord_slot_bytes(int cap) { return size_t(cap) * 12; }
 static void coord_release(krcn_csr* h) {
   CoordWs* w = h->cw;
   if (!w) return;
-  if (w->dev) {
-    (void)hipFree(w->dev);
-    h->owned -= w->dev_bytes;
-  }
+  (void)h->own.release(&w->dev);
   if (w->pin) (void)hipHostFree(w->pin);
   for (hipEvent_t e : w->ev)
     if (e) (void)hipEventDestroy(e);
@@ -64,9 +60,7 @@ static krcn_status coord_reserve(krcn_csr* h, int k, hipStream_t s) {
   }
   CoordWs* w = new CoordWs();
   h->cw = w;
-  w->dev_bytes = coord_slot_bytes(cap) + size_t(cap) * size_t(cap) * sizeof(double);
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(&w->dev), w->dev_bytes));
-  h->owned += w->dev_bytes;
+  CHK(h->own.alloc(&w->dev, coord_slot_bytes(cap) + size_t(cap) * size_t(cap) * sizeof(double)));
   w->delta = reinterpret_cast<double*>(w->dev);
   w->cols = reinterpret_cast<int*>(w->dev + size_t(cap) * 8);
   w->res = reinterpret_cast<double*>(w->dev + coord_slot_bytes(cap));

@@ -1,7 +1,10 @@
 // krcn_internal.hpp — shared host-side internals of libkrcn.so (not part of the ABI).
 //
 // The library is split into translation units that compile in parallel:
-//   krcn_plan.hip        handle lifecycle, transposed CSR, pass plans, comm, profiling
+//   krcn_handle.hip      error recorder, handle lifecycle, transposed CSR, setters / getters, profiling
+//   krcn_plan.hip        the pass-plan builders, ensure_plans, the reorth workspace
+//   krcn_place.hip       the placement probe and the placement search over Lanczos calls
+//   krcn_comm.hip        the RCCL communicator and the virtual communicator
 //   krcn_ops.hip         objective pieces (Ax, X^T u, weights, HVP, gradient, loss, dots)
 //   krcn_coord.hip       coordinate blocks of SSCN (gradient, Hessian block, Ax update)
 //   krcn_lanczos_f64.hip / krcn_lanczos_f32.hip
@@ -98,7 +101,7 @@ inline int cgs_rdv_chunks_of(int64_t nv) { return cgs_rdv_chunks(nv, cgs_rdv_ste
 #define LAUNCHCHK() HIPCHK(hipGetLastError())
 
 // ----------------------------------------------------------------- handles
-struct VirtualGroup;   // krcn_plan.hip: the ranks of a virtual communicator
+struct VirtualGroup;   // krcn_comm.hip: the ranks of a virtual communicator
 constexpr int kVirtualMaxRanks = 16;
 constexpr int kVirtualTimeoutS = 90;    // a rank that never arrives breaks the group after this (under
                                         // the GPU box's 180 s silence limit: a stall fails, not hangs)
@@ -128,7 +131,7 @@ std::mutex& build_mutex();
 
 // All-reduce of a virtual communicator: every rank's host thread drains its
 // stream, the last to arrive sums the ranks' buffers in rank order on the
-// device and writes the sum back to each of them (krcn_plan.hip).
+// device and writes the sum back to each of them (krcn_comm.hip).
 krcn_status virtual_allreduce(krcn_comm* c, void* buf, int64_t count, int dtype, hipStream_t s);
 
 struct ProfRec {
@@ -137,8 +140,82 @@ struct ProfRec {
   bool mid = false;
 };
 
-// Execution plan of one SpMV direction (pass 1: X, pass 2: X^T).
-struct PassPlan {
+// Owner of persistent device buffers: for every allocation the address of the
+// field that holds it and its byte size.  Teardown, owned_bytes and the
+// placement slots are all read from this table, so a buffer is named once,
+// where it is allocated.  The table holds addresses of its owner's fields:
+// it does not copy (a PassPlan resets through free_plan, a handle lives on
+// the heap).
+struct DevOwner {
+  struct Slot {
+    void** field;
+    size_t bytes;
+  };
+  std::vector<Slot> slots;
+  DevOwner() = default;
+  DevOwner(const DevOwner&) = delete;
+  DevOwner& operator=(const DevOwner&) = delete;
+  template <typename T>
+  krcn_status alloc(T** field, size_t bytes) {
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(field), bytes));
+    slots.push_back(Slot{reinterpret_cast<void**>(field), bytes});
+    return KRCN_OK;
+  }
+  const Slot* find(const void* field) const {
+    for (const Slot& s : slots)
+      if (s.field == field) return &s;
+    return nullptr;
+  }
+  // frees one field's buffer early and drops its bytes (a field the table does not hold: nothing)
+  krcn_status release(void* field) {
+    for (size_t i = 0; i < slots.size(); ++i)
+      if (slots[i].field == field) {
+        void* b = *slots[i].field;
+        *slots[i].field = nullptr;
+        slots.erase(slots.begin() + long(i));
+        if (b) HIPCHK(hipFree(b));
+        break;
+      }
+    return KRCN_OK;
+  }
+  void free_all() {
+    for (const Slot& s : slots) {
+      if (*s.field) (void)hipFree(*s.field);
+      *s.field = nullptr;
+    }
+    slots.clear();
+  }
+  size_t bytes() const {
+    size_t b = 0;
+    for (const Slot& s : slots) b += s.bytes;
+    return b;
+  }
+};
+
+// A temporary device allocation of a build: freed at scope exit (every early
+// return included), or earlier by reset() where a later allocation is meant
+// to reuse its space.  No conversion to T*: a kernel launch packs its
+// arguments by their own types, so the pointer is always passed as .p.
+template <typename T>
+struct DevTmp {
+  T* p = nullptr;
+  DevTmp() = default;
+  DevTmp(const DevTmp&) = delete;
+  DevTmp& operator=(const DevTmp&) = delete;
+  ~DevTmp() { reset(); }
+  krcn_status alloc(size_t bytes) {
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&p), bytes));
+    return KRCN_OK;
+  }
+  void reset() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+  }
+};
+
+// Execution plan of one SpMV direction (pass 1: X, pass 2: X^T): its fields,
+// which free_plan resets to these defaults ...
+struct PlanFields {
   int S = 1, groups = 1, L = 1, grid = 1, combine_grid = 1, ntiles = 0;
   int rows = 0;
   int64_t cols = 0, nnz = 0;
@@ -153,9 +230,9 @@ struct PassPlan {
   void* part = nullptr;       // S * rows partial row sums (sliced)
   int sorted = 0;             // sorted block tiles (k_sorted_pass) instead of wave tiles
   int sort_nt = 256;          // sorted tiles: threads per block (tile = kSortPerThread x sort_nt nonzeros)
-  int* tmid = nullptr;        // sorted tiles: first single-long-row tile of each group
   unsigned* gword = nullptr;  // sorted tiles: (column - tile base) << kSortSlotBits | CSR slot
   void* gval = nullptr;       //               value, same (tile-sorted) order
+  int* tmid = nullptr;        // sorted tiles: first single-long-row tile of each group
   int win = 0;                // LDS-window format (k_window_pass)
   int accum = 0;              //   1: every block walks all slices of its tile range (no partials)
   int R = 64;                 //   rows per tile (one lane per row)
@@ -185,8 +262,11 @@ struct PassPlan {
   unsigned short* xrow = nullptr;  //   row offsets in the block's rows, column-major per block
   void* xval = nullptr;
   void* xpart = nullptr;      //   per block X^T u partials (grid x cols)
-  size_t owned = 0;
   int64_t pcap = 0;           // entries of the handle's partials buffers (ensure_plans)
+};
+// ... and the owner of every device buffer those fields point to.
+struct PassPlan : PlanFields {
+  DevOwner own;
 };
 
 struct CoordWs;   // krcn_coord.hip: the workspace of the coordinate calls
@@ -240,9 +320,9 @@ struct krcn_csr {
   int reorth_m = 0;           // CGS2 workspace reserved for Lanczos m <= this (krcn_csr_reserve)
   void* cg_r = nullptr;       // CG vectors r | p | q (3 d-vectors, krcn_cg_solve)
   struct krcn::CgState* cg_st = nullptr;
-  CoordWs* cw = nullptr;      // coordinate workspace (first krcn_coord_* call; its device bytes are in owned)
+  CoordWs* cw = nullptr;      // coordinate workspace (first krcn_coord_* call; its device block is in own)
   int coord_window = 0;       // krcn_csr_set_coord_window (0: auto)
-  size_t owned = 0;
+  DevOwner own;               // every device buffer above but betas_dev (it aliases alphas_dev)
   krcn_comm* comm = nullptr;
   bool prof = false;
   std::vector<ProfRec> prof_pool;
@@ -258,7 +338,7 @@ struct krcn_csr {
   uint64_t gkey[kGraphKey] = {};    // arguments gexec was recorded with
   uint64_t glast[kGraphKey] = {};   // arguments of the previous call
   // row shards of a multi-rank communicator: what every rank's early-alpha
-  // Lanczos step must agree on (krcn_plan.hip agree_rows, after each plan build)
+  // Lanczos step must agree on (krcn_handle.hip agree_rows, after each plan build)
   int rows_pq = -1;            // packed alpha partials = max over ranks of pass_partials(p1); -1: not agreed
   int rows_early = 0;          // every rank's pass-1 grids fit kMaxPartials
   // placement probe of the hot buffers (ensure_plans, krcn_csr_set_placement_trials)
@@ -268,7 +348,7 @@ struct krcn_csr {
   int place_best = -1;         // the one kept
   float place_us[kPlaceMax] = {};   // probe HVP time of each (us)
   double place_hot_mb = 0.0;   // hot bytes the auto rule saw
-  // the placement search over the first Lanczos calls (krcn_plan.hip lzp_*)
+  // the placement search over the first Lanczos calls (krcn_place.hip lzp_*)
   int lzp_stage = 0;           // 0: not started; s >= 1: the next call times placement s - 1; -1: done
   int lzp_m = 0;               // the m the timed calls share
   int lzp_ran = 0, lzp_best = -1;
@@ -277,14 +357,23 @@ struct krcn_csr {
   hipEvent_t lzp_e0 = nullptr, lzp_e1 = nullptr;
 };
 
+constexpr int kNumCUs = 256;   // MI355X: 8 XCDs x 32 CUs
+
 void free_plan(PassPlan& P);
 void coord_free(krcn_csr* h);   // krcn_coord.hip: releases h->cw
 krcn_status ensure_plans(krcn_csr* h);
+// Row shards agree on the packed alpha partials (krcn_handle.hip; collective).
+krcn_status agree_rows(krcn_csr* h);
+// The handle's hot buffers as relocatable slots (krcn_place.hip): the plans'
+// tables and the handle's u, tn, W, td, pa, pb, pz, pq.
+void hot_slots(krcn_csr* h, std::vector<DevOwner::Slot>& out);
+// The placement probe of a plan build (krcn_place.hip; ensure_plans ends with it).
+krcn_status tune_placement(krcn_csr* h);
 // `reps` back-to-back local HVPs (pass 1 and pass 2 of the handle's plans, no
 // collective) on the handle's scratch vectors: *us = microseconds per HVP
 // (krcn_ops.hip; the placement probe of ensure_plans).
 krcn_status placement_probe(krcn_csr* h, hipStream_t s, int reps, float* us);
-// The placement search over Lanczos calls (krcn_plan.hip): lzp_begin before
+// The placement search over Lanczos calls (krcn_place.hip): lzp_begin before
 // a call's launches (may relocate the hot buffers on stream s and start the
 // timing), lzp_end after them, lzp_done after the call's synchronisation.
 krcn_status lzp_begin(krcn_csr* h, int m, hipStream_t s, bool* timed);
@@ -359,12 +448,10 @@ inline krcn_status set_device(const krcn_csr* h) {
   return KRCN_OK;
 }
 
+// count elements (at least one) into a field of the handle
 template <typename T>
 inline krcn_status dalloc(krcn_csr* h, T** p, size_t count) {
-  if (count == 0) count = 1;
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T)));
-  h->owned += count * sizeof(T);
-  return KRCN_OK;
+  return h->own.alloc(p, std::max<size_t>(count, 1) * sizeof(T));
 }
 
 inline krcn_status nccl_dtype(int dtype, ncclDataType_t* t) {
@@ -653,7 +740,7 @@ inline krcn_status run_pass(PassPlan& P, const Src& first, const Src2& rest, con
 // The number of partials run_pass writes for plan P when its epilogue
 // reduces (the *Pout of a non-fused launch): the combine's grid for sliced
 // plans, the main launch's otherwise.  Row shards agree on its maximum over
-// ranks before the collectives (krcn_plan.hip agree_rows).
+// ranks before the collectives (krcn_handle.hip agree_rows).
 inline int pass_partials(const PassPlan& P) {
   auto combine = [&](int S) {
     if (S <= kCombineSmallS) return combine_small_grid(P.rows);

@@ -700,7 +700,7 @@ static krcn_status lanczos_impl(krcn_csr* h, const T* w, const T* g, int m, int 
     std::copy(key, key + krcn_csr::kGraphKey, h->gkey);
     HIPCHK(hipGraphLaunch(h->gexec, s_call));
   } else {
-    bool timed = false;   // a call of the placement search (krcn_plan.hip lzp_*)
+    bool timed = false;   // a call of the placement search (krcn_place.hip lzp_*)
     CHK(lzp_begin(h, m, s, &timed));
     CHK(enqueue());
     CHK(lzp_end(h, s, timed));

@@ -101,7 +101,7 @@ extern "C" krcn_status krcn_hvp(krcn_csr* h, const void* w, const void* v, void*
                                static_cast<float*>(y), l2, S(stream));
 }
 
-// The placement probe (krcn_plan.hip tune_placement): the two local passes of
+// The placement probe (krcn_place.hip tune_placement): the two local passes of
 // an HVP (pass 1 with the weighting, pass 2 with y = s / n; no collective, so
 // a rank of a sharded handle probes alone) over the handle's own scratch:
 // w = tn, v = W, y = td.  Their values do not change the memory traffic.

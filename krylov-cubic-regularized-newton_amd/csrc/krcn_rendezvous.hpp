@@ -1,5 +1,5 @@
 // krcn_rendezvous.hpp — the rendezvous of a virtual communicator's rank
-// threads (host-only; krcn_comm_create_virtual in krcn_plan.hip, and the
+// threads (host-only; krcn_comm_create_virtual in krcn_comm.hip, and the
 // sanitizer stress test tests/native/rendezvous_stress.cpp).
 //
 // Every rank thread of the group calls arrive() once per all-reduce, in the

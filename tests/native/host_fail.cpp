@@ -1,5 +1,5 @@
 // fail() / krcn_last_error_string for the host-only sanitizer builds (the
-// library's own are in krcn_plan.hip, next to the HIP code).
+// library's own are in krcn_handle.hip, next to the HIP code).
 #include <cstdarg>
 #include <cstdio>
 #include <string>

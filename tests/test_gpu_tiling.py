@@ -150,3 +150,22 @@ def test_sliced_equals_unsliced_within_rounding(problem):
     y0 = krcn.DeviceCSR(A, slicing=1).hvp(t(w), t(v)).cpu().numpy()
     y8 = krcn.DeviceCSR(A, slicing=8).hvp(t(w), t(v)).cpu().numpy()
     assert rel_err(y8, y0) < 1e-14
+
+
+def test_owned_bytes_sliced_sorted_counts_held_buffers():
+    """owned_bytes() is the bytes the handle holds.  A sliced sorted plan swaps
+    the slice copies idx + val for gword + gval of equal size, so it differs
+    from the sliced wave plan of the same matrix only by the tile tables and
+    tmid (tens of KB here): less than 6 nnz bytes.  (An accounting that keeps
+    the freed slice copies is off by 12 nnz per pass.)"""
+    A = sp.random(4000, 3000, density=0.005, format="csr", dtype=np.float64,
+                  random_state=np.random.default_rng(7))
+    A.sort_indices()
+    Xw = krcn.DeviceCSR(A, slicing=8, fmt=krcn.KRCN_FORMAT_WAVE)
+    Xs = krcn.DeviceCSR(A, slicing=8, fmt=krcn.KRCN_FORMAT_SORTED)
+    iw, is_ = Xw.plan_info(), Xs.plan_info()
+    assert (iw["pass1"][0], iw["pass2"][0]) == (8, 8)
+    assert (is_["pass1"][0], is_["pass2"][0]) == (-8, -8)
+    diff = abs(Xw.owned_bytes() - Xs.owned_bytes())
+    print(f"owned_bytes wave {Xw.owned_bytes()} sorted {Xs.owned_bytes()} diff {diff} (6 nnz = {6 * A.nnz})")
+    assert diff < 6 * A.nnz

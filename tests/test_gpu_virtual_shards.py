@@ -158,7 +158,7 @@ def test_rows_x2_unequal_blocks_agree():
     follows its own block.  On a skewed matrix the nnz-balanced split gives
     the two ranks blocks of very different row counts (so different pass-1
     grids); the ranks agree on the packed length at attach time
-    (krcn_plan.hip agree_rows), the shorter one zero-fills, and the recurrence
+    (krcn_handle.hip agree_rows), the shorter one zero-fills, and the recurrence
     must still match the oracle at the golden tolerance (alphas / betas 1e-11,
     m = 10; reference cubic.py:77-111 over loss.py:289-302)."""
     import scipy.sparse as sp
