@@ -94,13 +94,38 @@ enum { KRCN_SLICING_AUTO = 0, KRCN_SLICING_OFF = 1 };
  * gathered vector into LDS and sums each row in one lane (short rows),
  * KRCN_FORMAT_JAG gives every lane a row and stores the elements level by level
  * so that the whole LDS holds the gathered vector (one window, or two
- * double-buffered windows walked by every block; scipy's summation order). */
+ * double-buffered windows walked by every block; scipy's summation order).
+ * KRCN_FORMAT_DENSE (nearly dense matrices) stores no indices:
+ *   - Storage: each dense pass owns a row-major image of its own matrix (X for
+ *     pass 1, n rows; X^T for pass 2, d rows), rows padded to whole 16-byte
+ *     vectors, entries absent from the CSR stored as zeros: rows x ld x
+ *     sizeof(dtype) device bytes per pass (krcn_dense_geometry reports them),
+ *     about 2 n d sizeof(dtype) for both, counted by krcn_csr_owned_bytes.
+ *     The plan build checks that the images fit the device's free memory
+ *     before it allocates anything and returns KRCN_ERR_UNSUPPORTED (needed
+ *     and free bytes in the message) otherwise, leaving the handle as it was.
+ *   - Summation order: a row is summed by L lanes; lane l adds the products
+ *     of the row's 16-byte vectors l, l + L, ... left to right, entry by
+ *     entry; the L lane sums are combined by an xor butterfly, and the sums
+ *     of column slices (few, long rows) are added in slice order.  Under
+ *     KRCN_LANES_SEQUENTIAL a row is one left-to-right sum without FMA
+ *     contraction: scipy's csr_matvec / csc_matvec bits for finite vectors.
+ *   - Non-finite vectors: a dense pass multiplies the stored zeros, so an inf
+ *     or nan in the gathered vector reaches every row, not only the rows that
+ *     hold a nonzero in that column.  For finite vectors nothing changes.
+ *   - Explicit stored zeros and rows with unsorted columns are fine.  Repeated
+ *     entries are not supported: krcn_csr_create, and through it the
+ *     transposed CSR that the coordinate calls and krcn_csr_get_transpose
+ *     use, keep their duplicate-free-input assumption.
+ *   - Never picked by KRCN_FORMAT_AUTO; one pass may be dense while the other
+ *     keeps a CSR format (krcn_csr_set_pass_format).  Sharded handles return
+ *     KRCN_ERR_UNSUPPORTED from the setters. */
 enum { KRCN_FORMAT_AUTO = 0, KRCN_FORMAT_WAVE = 1, KRCN_FORMAT_SORTED = 2, KRCN_FORMAT_WINDOW = 3,
-       KRCN_FORMAT_JAG = 4 };
+       KRCN_FORMAT_JAG = 4, KRCN_FORMAT_DENSE = 5 };
 
 /* Formats reported by krcn_csr_plan_format. */
 enum { KRCN_PLAN_WAVE = 1, KRCN_PLAN_SORTED = 2, KRCN_PLAN_WINDOW_SLICES = 3, KRCN_PLAN_WINDOW_ACCUM = 4,
-       KRCN_PLAN_JAG = 5 };
+       KRCN_PLAN_JAG = 5, KRCN_PLAN_DENSE = 6 };
 
 typedef struct krcn_csr krcn_csr;
 typedef struct krcn_comm krcn_comm;
@@ -160,10 +185,19 @@ krcn_status krcn_csr_set_format(krcn_csr* h, int format);
 krcn_status krcn_csr_set_pass_format(krcn_csr* h, int pass, int format);
 /* Execution plan summary (builds the plan if needed):
  * out8_host = {slices, lanes, tiles, grid} of pass 1 (X) then pass 2 (X^T);
- * a sorted-tile pass reports its slice count negated. */
+ * a sorted-tile pass reports its slice count negated; a dense pass reports
+ * {slices, lanes, row groups, grid}. */
 krcn_status krcn_csr_plan_info(krcn_csr* h, int* out8_host);
 /* Format of each pass's plan (KRCN_PLAN_*): out2_host = {pass 1, pass 2}. */
 krcn_status krcn_csr_plan_format(krcn_csr* h, int* out2_host);
+/* Geometry of a dense pass (KRCN_FORMAT_DENSE) over a rows x cols matrix under
+ * a lane and a slicing policy (as krcn_csr_set_lanes / krcn_csr_set_slicing
+ * take them).  Host arithmetic only: needs no device.
+ * out_host (8 entries) = {ld (entries per image row), lanes, slices, entries
+ * of the widest slice, row groups, grid, image bytes (saturating at
+ * INT64_MAX), 16-byte vectors per row}. */
+krcn_status krcn_dense_geometry(int64_t rows, int64_t cols, int dtype, int lanes, int slicing,
+                                int64_t* out_host);
 /* Read back the transposed CSR (tests): colptr (d+1), rowidx (nnz), vals (nnz). */
 krcn_status krcn_csr_get_transpose(const krcn_csr* h, int32_t* colptr,
                                    int32_t* rowidx, void* vals, void* stream);

@@ -280,8 +280,10 @@ extern "C" krcn_status krcn_csr_set_slicing(krcn_csr* h, int slicing) {
 
 extern "C" krcn_status krcn_csr_set_format(krcn_csr* h, int format) {
   if (!h) return fail(KRCN_ERR_INVALID, "krcn_csr_set_format: null handle");
-  if (format < KRCN_FORMAT_AUTO || format > KRCN_FORMAT_JAG)
-    return fail(KRCN_ERR_INVALID, "krcn_csr_set_format: expected 0 (auto), 1 (wave), 2 (sorted), 3 (window) or 4 (jagged)");
+  if (format < KRCN_FORMAT_AUTO || format > KRCN_FORMAT_DENSE)
+    return fail(KRCN_ERR_INVALID, "krcn_csr_set_format: expected 0 (auto), 1 (wave), 2 (sorted), 3 (window), 4 (jagged) or 5 (dense)");
+  if (format == KRCN_FORMAT_DENSE && h->shard != KRCN_SHARD_NONE)
+    return fail(KRCN_ERR_UNSUPPORTED, "krcn_csr_set_format: the dense format does not run on a sharded handle");
   if (h->format != format) {
     h->format = format;
     h->plans_ready = false;
@@ -292,8 +294,10 @@ extern "C" krcn_status krcn_csr_set_format(krcn_csr* h, int format) {
 extern "C" krcn_status krcn_csr_set_pass_format(krcn_csr* h, int pass, int format) {
   if (!h) return fail(KRCN_ERR_INVALID, "krcn_csr_set_pass_format: null handle");
   if (pass != 1 && pass != 2) return fail(KRCN_ERR_INVALID, "krcn_csr_set_pass_format: pass must be 1 (X) or 2 (X^T)");
-  if (format < -1 || format > KRCN_FORMAT_JAG)
+  if (format < -1 || format > KRCN_FORMAT_DENSE)
     return fail(KRCN_ERR_INVALID, "krcn_csr_set_pass_format: expected -1 (the handle's format) or a KRCN_FORMAT_* value");
+  if (format == KRCN_FORMAT_DENSE && h->shard != KRCN_SHARD_NONE)
+    return fail(KRCN_ERR_UNSUPPORTED, "krcn_csr_set_pass_format: the dense format does not run on a sharded handle");
   if (h->format_pass[pass - 1] != format) {
     h->format_pass[pass - 1] = format;
     h->plans_ready = false;
@@ -357,7 +361,8 @@ extern "C" krcn_status krcn_csr_plan_format(krcn_csr* h, int* out2_host) {
   CHK(ensure_plans(h));
   const PassPlan* ps[2] = {&h->p1, &h->p2};
   for (int i = 0; i < 2; ++i)
-    out2_host[i] = ps[i]->jag   ? KRCN_PLAN_JAG
+    out2_host[i] = ps[i]->dense ? KRCN_PLAN_DENSE
+                   : ps[i]->jag ? KRCN_PLAN_JAG
                    : ps[i]->win ? (ps[i]->accum ? KRCN_PLAN_WINDOW_ACCUM : KRCN_PLAN_WINDOW_SLICES)
                    : ps[i]->sorted ? KRCN_PLAN_SORTED : KRCN_PLAN_WAVE;
   return KRCN_OK;

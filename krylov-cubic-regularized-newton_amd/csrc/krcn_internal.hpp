@@ -19,6 +19,7 @@
 #include "krcn_tiled.hpp"
 #include "krcn_window.hpp"
 #include "krcn_jag.hpp"
+#include "krcn_dense.hpp"
 #include "krcn_cg.hpp"
 #include "krcn_cgs2.hpp"
 
@@ -262,6 +263,8 @@ struct PlanFields {
   unsigned short* xrow = nullptr;  //   row offsets in the block's rows, column-major per block
   void* xval = nullptr;
   void* xpart = nullptr;      //   per block X^T u partials (grid x cols)
+  int dense = 0;              // dense format (k_dense_pass; S, L, grid, ntiles = row groups, own_val = the image)
+  int64_t dld = 0;            //   entries per image row
   int64_t pcap = 0;           // entries of the handle's partials buffers (ensure_plans)
 };
 // ... and the owner of every device buffer those fields point to.
@@ -541,6 +544,7 @@ template <typename T, class Src, class Src2, class Epi>
 inline krcn_status run_pass(PassPlan& P, const Src& first, const Src2& rest, const Epi& epi, double* partials,
                             int* Pout, hipStream_t s, ProfRec* mid = nullptr) {
   // a reducing launch writes one partial per block: the buffer must hold them
+  // (dense plans as wave tiles: the combine's grid when sliced, else the main launch's)
   const int reducer_grid = P.jag ? (P.jG > 1 ? P.combine_grid : P.grid)
                                  : (P.win ? !P.accum : P.S > 1) ? P.combine_grid : P.grid;
   if (partials && reducer_grid > P.pcap)
@@ -564,6 +568,38 @@ inline krcn_status run_pass(PassPlan& P, const Src& first, const Src2& rest, con
     if (Pout) *Pout = P.grid;
     return KRCN_OK;
   } else {
+  if (P.dense) {
+    // dense plans run the generic step only: the sources of the fused steps
+    // are never selected for one (lanczos_impl: fuse, fuse_u and early need a
+    // window, sorted or jagged pass 1)
+    if constexpr (IsLzZ<Src>::value || IsLzU<Src>::value) {
+      return fail(KRCN_ERR_UNSUPPORTED, "fused Lanczos steps do not run over a dense plan");
+    } else {
+      DenseArgs da{P.rows, P.S, P.ntiles, P.cols, P.dld, P.dld / int64_t(16 / sizeof(T)), P.val};
+      with_lanes(P.L, [&](auto lc) {
+        constexpr int LL = decltype(lc)::value;
+        if (P.S == 1) {
+          hipLaunchKernelGGL((k_dense_pass<T, LL, Src, Epi>), dim3(P.grid), dim3(kDenseNT), 0, s, da, first, epi,
+                             partials);
+        } else {
+          EpiSlicePart<T> ep{static_cast<T*>(P.part), int64_t(P.rows)};
+          hipLaunchKernelGGL((k_dense_pass<T, LL, Src, EpiSlicePart<T>>), dim3(P.grid), dim3(kDenseNT), 0, s, da,
+                             first, ep, static_cast<double*>(nullptr));
+        }
+      });
+      LAUNCHCHK();
+      if (mid && P.S > 1) {
+        HIPCHK(hipEventRecord(mid->em, s));
+        mid->mid = true;
+      }
+      if (P.S > 1) {
+        CHK(run_combine<T>(P, P.S, rest, epi, partials, Pout, s));
+      } else if (Pout) {
+        *Pout = P.grid;
+      }
+      return KRCN_OK;
+    }
+  }
   if constexpr (IsLzU<Src>::value) {
     if (!P.jag || P.S != 1)
       return fail(KRCN_ERR_UNSUPPORTED, "the two-launch Lanczos pass 2 needs a single-window jagged plan");
@@ -750,7 +786,7 @@ inline int pass_partials(const PassPlan& P) {
   };
   if (P.jag) return (P.S > 1 && P.jG > 1) ? combine(P.jG) : P.grid;
   if (P.win) return P.accum ? P.grid : combine(P.S);
-  return P.S > 1 ? combine(P.S) : P.grid;
+  return P.S > 1 ? combine(P.S) : P.grid;   // wave, sorted and dense plans
 }
 
 #if KRCN_FOLD

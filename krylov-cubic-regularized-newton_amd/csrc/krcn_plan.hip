@@ -1003,20 +1003,79 @@ static krcn_status build_jag(PassPlan& P, const int* ptr, const int* idx, const 
   return KRCN_OK;
 }
 
+// ----------------------------------------------------------- dense format
+// The image of one pass (krcn_dense.hpp): zero fill plus a scatter of the CSR
+// on the build stream; the slice partials when the geometry slices the pass.
+template <typename T>
+static krcn_status build_dense(PassPlan& P, const int* ptr, const int* idx, const T* val, int lanes, int slicing,
+                               hipStream_t s) {
+  const DenseGeom g = dense_geometry(P.rows, P.cols, sizeof(T), lanes, slicing);
+  CHK(P.own.alloc(&P.own_val, size_t(g.bytes)));
+  HIPCHK(hipMemsetAsync(P.own_val, 0, size_t(g.bytes), s));
+  if (P.nnz > 0) {
+    const int64_t blocks = (int64_t(P.rows) + kDenseNT / 64 - 1) / (kDenseNT / 64);
+    hipLaunchKernelGGL((k_dense_scatter<T>), dim3(unsigned(std::min<int64_t>(blocks, 65536))), dim3(kDenseNT), 0, s,
+                       P.rows, ptr, idx, val, g.ld, static_cast<T*>(P.own_val));
+    LAUNCHCHK();
+  }
+  if (g.S > 1) CHK(P.own.alloc(&P.part, sizeof(T) * size_t(g.S) * size_t(std::max(P.rows, 1))));
+  HIPCHK(hipStreamSynchronize(s));
+  P.dense = 1;
+  P.dld = g.ld;
+  P.S = g.S;
+  P.L = g.L;
+  P.ntiles = int(g.groups);
+  P.grid = g.grid;
+  P.combine_grid = combine_grid(P.rows);
+  P.val = P.own_val;
+  return KRCN_OK;
+}
+
+// The format policy of one pass: krcn_csr_set_pass_format over
+// krcn_csr_set_format, under the A/B knobs KRCN_FMT1 / KRCN_FMT2 (KRCN_FORMAT_*
+// values; unset keeps the handle's).
+static int pass_format(const krcn_csr* h, int pass) {
+  int fmt = h->format_pass[pass - 1] >= 0 ? h->format_pass[pass - 1] : h->format;
+  static const int f1 = [] { const char* e = tuning_env("KRCN_FMT1"); return e ? atoi(e) : -1; }();
+  static const int f2 = [] { const char* e = tuning_env("KRCN_FMT2"); return e ? atoi(e) : -1; }();
+  const int f = pass == 2 ? f2 : f1;
+  if (f >= KRCN_FORMAT_AUTO && f <= KRCN_FORMAT_DENSE) fmt = f;
+  return fmt;
+}
+
+extern "C" krcn_status krcn_dense_geometry(int64_t rows, int64_t cols, int dtype, int lanes, int slicing,
+                                           int64_t* out_host) {
+  if (!out_host) return fail(KRCN_ERR_INVALID, "krcn_dense_geometry: null argument");
+  if (rows < 0 || cols < 0 || rows > INT32_MAX || cols > INT32_MAX || (dtype != KRCN_F64 && dtype != KRCN_F32))
+    return fail(KRCN_ERR_INVALID, "krcn_dense_geometry: expected 0 <= rows, cols < 2^31 and a KRCN_F64 / KRCN_F32 dtype");
+  const bool lanes_ok = lanes == KRCN_LANES_AUTO || lanes == KRCN_LANES_SEQUENTIAL ||
+                        (lanes >= 2 && lanes <= 64 && (lanes & (lanes - 1)) == 0);
+  const bool slicing_ok = slicing == KRCN_SLICING_AUTO || slicing == KRCN_SLICING_OFF || (slicing >= 8 && slicing % 8 == 0);
+  if (!lanes_ok || !slicing_ok)
+    return fail(KRCN_ERR_INVALID, "krcn_dense_geometry: lanes and slicing as krcn_csr_set_lanes / krcn_csr_set_slicing take them");
+  const DenseGeom g = dense_geometry(rows, cols, dtype == KRCN_F64 ? 8 : 4, lanes, slicing);
+  out_host[0] = g.ld;
+  out_host[1] = g.L;
+  out_host[2] = g.S;
+  out_host[3] = g.width;
+  out_host[4] = g.groups;
+  out_host[5] = g.grid;
+  out_host[6] = g.bytes;
+  out_host[7] = g.nvec;
+  return KRCN_OK;
+}
+
 template <typename T>
 static krcn_status build_plan(krcn_csr* h, int pass, int rows, int64_t cols, int64_t nnz, const int* ptr,
                               const int* idx, const T* val, int lanes, hipStream_t s) {
   PassPlan& P = pass == 2 ? h->p2 : h->p1;
   reset_plan(P, rows, cols, nnz);
   const bool seq = lanes == KRCN_LANES_SEQUENTIAL;
-  // A/B knobs KRCN_FMT1 / KRCN_FMT2: the format policy of one pass only
-  // (KRCN_FORMAT_* values; unset keeps the handle's)
-  int fmt = h->format_pass[pass - 1] >= 0 ? h->format_pass[pass - 1] : h->format;
-  {
-    static const int f1 = [] { const char* e = tuning_env("KRCN_FMT1"); return e ? atoi(e) : -1; }();
-    static const int f2 = [] { const char* e = tuning_env("KRCN_FMT2"); return e ? atoi(e) : -1; }();
-    const int f = pass == 2 ? f2 : f1;
-    if (f >= KRCN_FORMAT_AUTO && f <= KRCN_FORMAT_JAG) fmt = f;
+  const int fmt = pass_format(h, pass);
+  if (fmt == KRCN_FORMAT_DENSE) {
+    if (h->shard != KRCN_SHARD_NONE)
+      return fail(KRCN_ERR_UNSUPPORTED, "the dense format does not run on a sharded handle");
+    return build_dense<T>(P, ptr, idx, val, lanes, h->slicing, s);
   }
   // jagged format: forced, or by the auto policy (its summation order is
   // scipy's, so the sequential lane policy may use it too)
@@ -1129,6 +1188,26 @@ static krcn_status build_plan(krcn_csr* h, int pass, int rows, int64_t cols, int
 
 template <typename T>
 static krcn_status build_plans(krcn_csr* h, bool lz2, hipStream_t s) {
+  // dense passes: the images must fit the device's free memory (with what the
+  // plans about to be replaced give back), checked before anything is
+  // allocated or freed so that a refusal leaves the handle as it was
+  {
+    const bool dn[2] = {pass_format(h, 1) == KRCN_FORMAT_DENSE, pass_format(h, 2) == KRCN_FORMAT_DENSE};
+    if ((dn[0] || dn[1]) && h->shard == KRCN_SHARD_NONE) {
+      const int64_t b1 = dn[0] ? dense_geometry(h->n, h->d, sizeof(T), h->lanes_x, h->slicing).bytes : 0;
+      const int64_t b2 = dn[1] ? dense_geometry(h->d, h->n, sizeof(T), h->lanes_xt, h->slicing).bytes : 0;
+      const int64_t need = b1 > INT64_MAX - b2 ? INT64_MAX : b1 + b2;
+      size_t mfree = 0, mtotal = 0;
+      HIPCHK(hipMemGetInfo(&mfree, &mtotal));
+      const size_t avail = mfree + h->p1.own.bytes() + h->p2.own.bytes();
+      if (uint64_t(need) > uint64_t(avail))
+        return fail(KRCN_ERR_UNSUPPORTED, "the dense format needs %lld bytes of images for this %lld x %lld matrix, "
+                    "the device has %lld bytes free", (long long)need, (long long)h->n, (long long)h->d,
+                    (long long)avail);
+      free_plan(h->p1);   // (both before either image is allocated: the peak holds no old plan)
+      free_plan(h->p2);
+    }
+  }
   CHK(build_plan<T>(h, 2, int(h->d), h->n, h->nnz, h->tptr, h->tidx, static_cast<const T*>(h->tval), h->lanes_xt, s));
   h->p1_unsliced = lz2 && h->p2.jag && h->p2.S == 1 && h->shard == KRCN_SHARD_NONE;
   return build_plan<T>(h, 1, int(h->n), h->d, h->nnz, h->ptr, h->idx, static_cast<const T*>(h->val), h->lanes_x, s);

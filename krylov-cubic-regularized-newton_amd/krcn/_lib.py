@@ -23,7 +23,9 @@ KRCN_SHARD_NONE, KRCN_SHARD_ROWS, KRCN_SHARD_COLS = 0, 1, 2
 KRCN_LANES_AUTO, KRCN_LANES_SEQUENTIAL = 0, 1
 KRCN_SLICING_AUTO, KRCN_SLICING_OFF = 0, 1
 KRCN_FORMAT_AUTO, KRCN_FORMAT_WAVE, KRCN_FORMAT_SORTED, KRCN_FORMAT_WINDOW, KRCN_FORMAT_JAG = 0, 1, 2, 3, 4
+KRCN_FORMAT_DENSE = 5
 KRCN_PLAN_WAVE, KRCN_PLAN_SORTED, KRCN_PLAN_WINDOW_SLICES, KRCN_PLAN_WINDOW_ACCUM = 1, 2, 3, 4
+KRCN_PLAN_JAG, KRCN_PLAN_DENSE = 5, 6
 KRCN_SPACE_N, KRCN_SPACE_D = 0, 1
 KRCN_COORD_MAX = 1024
 
@@ -72,6 +74,7 @@ SIGNATURES = {
     "krcn_csr_placement_info": [_vp, _dp],
     "krcn_csr_plan_info": [_vp, ctypes.POINTER(ctypes.c_int)],
     "krcn_csr_plan_format": [_vp, ctypes.POINTER(ctypes.c_int)],
+    "krcn_dense_geometry": [_i64, _i64, _i, _i, _i, ctypes.POINTER(_i64)],
     "krcn_csr_get_transpose": [_vp, _vp, _vp, _vp, _vp],
     "krcn_csr_attach_comm": [_vp, _vp],
     "krcn_csr_reserve": [_vp, _i, _i],

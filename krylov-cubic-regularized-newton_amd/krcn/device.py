@@ -106,7 +106,8 @@ class DeviceCSR:
         self._replan()
 
     def set_format(self, fmt=0):
-        """Tile format: 0 auto, 1 wave tiles (CSR order), 2 sorted block tiles, 3 LDS windows, 4 jagged."""
+        """Tile format: 0 auto, 1 wave tiles (CSR order), 2 sorted block tiles, 3 LDS windows, 4 jagged,
+        5 dense (row-major images of X and X^T, no indices; never picked by auto)."""
         call("krcn_csr_set_format", self._h, int(fmt))
         self._replan()
 
@@ -153,15 +154,16 @@ class DeviceCSR:
                             "ms": [round(buf[16 + i], 4) for i in range(kl)]}}
 
     def plan_info(self):
-        """{'pass1': (slices, lanes, tiles, grid), 'pass2': (...)}; slices < 0 marks sorted tiles."""
+        """{'pass1': (slices, lanes, tiles, grid), 'pass2': (...)}; slices < 0 marks sorted tiles,
+        a dense pass reports its row groups as tiles."""
         buf = (ctypes.c_int * 8)()
         call("krcn_csr_plan_info", self._h, buf)
         return {"pass1": tuple(buf[0:4]), "pass2": tuple(buf[4:8])}
 
-    _FORMAT_NAMES = {1: "wave", 2: "sorted", 3: "window-slices", 4: "window-accum", 5: "jagged"}
+    _FORMAT_NAMES = {1: "wave", 2: "sorted", 3: "window-slices", 4: "window-accum", 5: "jagged", 6: "dense"}
 
     def plan_format(self):
-        """{'pass1': name, 'pass2': name}: wave, sorted, window-slices or window-accum."""
+        """{'pass1': name, 'pass2': name}: wave, sorted, window-slices, window-accum, jagged or dense."""
         buf = (ctypes.c_int * 2)()
         call("krcn_csr_plan_format", self._h, buf)
         return {"pass1": self._FORMAT_NAMES[buf[0]], "pass2": self._FORMAT_NAMES[buf[1]]}

@@ -128,6 +128,31 @@ def make_problem(config="news20", seed=SEED, skew=False, n=None, d=None, nnz=Non
     return A, b
 
 
+def make_dense_problem(n, d, fill, seed=SEED):
+    """Nearly dense problem in the shape of the reference driver's gisette / madelon / duke
+    (cubic_newton.py:38-49): (A, b) with A an n x d scipy CSR float64 (int32 indices, sorted
+    columns) in which entry (i, j) is present when uniform01 < fill, with a nonzero value in
+    [-1, 1], and b the +-1 labels of a planted model.  The entries absent from the CSR are
+    exact zeros of A.toarray().  Deterministic in (n, d, fill, seed)."""
+    n, d = int(n), int(d)
+    keep = (uniform01(seed, 21, n * d) < float(fill)).reshape(n, d)
+    vals = 2.0 * uniform01(seed, 22, n * d).reshape(n, d) - 1.0
+    vals[vals == 0.0] = 0.5   # a present entry is a nonzero
+    rows, cols = np.nonzero(keep)
+    indptr = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(keep.sum(axis=1), out=indptr[1:])
+    A = sp.csr_matrix((vals[rows, cols], cols.astype(np.int32), indptr.astype(np.int32)), shape=(n, d))
+    xstar = 2.0 * uniform01(seed, 23, d) - 1.0
+    noise = 2.0 * uniform01(seed, 24, n) - 1.0
+    b = np.where(A @ xstar + 0.1 * noise >= 0.0, 1.0, -1.0)
+    return A, b
+
+
+def dense_hvp_bytes(n, d, s_val=8):
+    """Algorithmic bytes of one HVP over dense images: 2 n d s + s (2d + 3n)."""
+    return 2 * n * d * s_val + s_val * (2 * d + 3 * n)
+
+
 def hvp_bytes(n, d, nnz, s_val=8, s_idx=4, s_ptr=4):
     """Algorithmic bytes of one HVP:
     2 nnz (s_val + s_idx) + s_ptr ((n+1) + (d+1)) + s_val (2d + 3n)."""

@@ -119,11 +119,20 @@ class LogisticRegression(Oracle):
     device / dtype: where and in which precision the device copy of A lives
     (fp64 by default, as the reference computes).  shard: optional
     krcn.dist.ShardSpec for multi-GPU runs (krcn.dist.shard_problem builds it).
+    format: None keeps the handle's format policy, "dense" stores A and A^T as
+    row-major images without indices (nearly dense A such as gisette, madelon
+    or duke; unsharded only), an int is a KRCN_FORMAT_* value.
     """
 
     def __init__(self, A, b, store_mat_vec_prod=False, *args, device=None, dtype=torch.float64,
-                 shard=None, lanes=(0, 0), **kwargs):
+                 shard=None, lanes=(0, 0), format=None, **kwargs):
         super().__init__(*args, **kwargs)
+        if format is None or (isinstance(format, (int, np.integer)) and not isinstance(format, bool)):
+            fmt = None if format is None else int(format)
+        elif format == "dense":
+            fmt = _lib.KRCN_FORMAT_DENSE
+        else:
+            raise ValueError(f"format must be None, 'dense' or a KRCN_FORMAT_* int, got {format!r}")
         import scipy.sparse as sp
         self.A = A
         self.b = _labels01(b)
@@ -136,8 +145,13 @@ class LogisticRegression(Oracle):
         mode = _lib.KRCN_SHARD_NONE if shard is None else shard.mode
         self.device_matrix = krcn.DeviceCSR(A_local, device=device, dtype=dtype,
                                             n_global=self.n, shard_mode=mode, lanes=lanes)
+        if fmt is not None:
+            self.device_matrix.set_format(fmt)
         if shard is not None and shard.comm is not None:
             self.device_matrix.attach_comm(shard.comm)
+        if fmt == _lib.KRCN_FORMAT_DENSE:
+            # the images are built here, not inside the first compute call
+            self.device_matrix.plan_info()
         self.device = self.device_matrix.device
         self.dtype = dtype
         self._b_dev = torch.from_numpy(b_local.astype(self._np_dtype())).to(self.device)
