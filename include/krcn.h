@@ -123,6 +123,42 @@ enum { KRCN_SLICING_AUTO = 0, KRCN_SLICING_OFF = 1 };
 enum { KRCN_FORMAT_AUTO = 0, KRCN_FORMAT_WAVE = 1, KRCN_FORMAT_SORTED = 2, KRCN_FORMAT_WINDOW = 3,
        KRCN_FORMAT_JAG = 4, KRCN_FORMAT_DENSE = 5 };
 
+/* Stored width of the matrix values in the pass plans.  Arithmetic, vectors
+ * and sums keep the handle's dtype.
+ * Only dense passes (KRCN_FORMAT_DENSE) honour the policy: a pass on a CSR
+ * format keeps full width and reports sizeof(dtype) from
+ * krcn_csr_plan_value_bytes.  On a KRCN_F32 handle every policy is a no-op
+ * (both passes report 4, results are bitwise the same).  The policy touches
+ * the pass plans only: krcn_csr_get_transpose and the coordinate calls
+ * (krcn_coord_*) read the handle's transposed CSR, which stays full width.
+ * A narrowed dense pass on a KRCN_F64 handle:
+ *   - Values: the image stores static_cast<float>(v) (round to nearest even);
+ *     the kernel widens each stored value to double, which is exact, and
+ *     products and sums are fp64.  The pass computes with A32 =
+ *     double(float(A)) and nothing else.  Values outside fp32's normal range
+ *     (overflow to inf, subnormal results, flush to zero) are the caller's
+ *     responsibility.
+ *   - Geometry: the dense geometry at 4-byte entries, four entries per 16-byte
+ *     vector, ld a multiple of 4, lanes and slices from ceil(cols / 4)
+ *     vectors: what krcn_dense_geometry(rows, cols, KRCN_F32, lanes, slicing,
+ *     ..) returns, and what krcn_csr_plan_info reports.
+ *   - Summation order: lane l of L adds the products of the 16-byte vectors
+ *     l, l + L, ... of the row's slice, within a vector entry by entry, left
+ *     to right (four entries per vector); then the xor butterfly, then the
+ *     slices in slice order.  Under KRCN_LANES_SEQUENTIAL a row is one
+ *     left-to-right sum without FMA contraction: scipy's csr_matvec /
+ *     csc_matvec on A32, bit for bit, for finite vectors.
+ *   - Memory: rows x ld x 4 image bytes per pass; the fit check against the
+ *     device's free memory and krcn_csr_owned_bytes count the narrowed bytes.
+ * KRCN_VALUES_F32_EXACT decides once per plan build, from a device scan of the
+ * handle's borrowed CSR data: if every value survives double(float(v)) == v
+ * (a NaN does not) the plans are bitwise those of KRCN_VALUES_F32, else
+ * bitwise those of KRCN_VALUES_FULL. */
+enum { KRCN_VALUES_FULL = 0,       /* the handle's dtype (default)                      */
+       KRCN_VALUES_F32 = 1,        /* fp32, each value rounded to nearest even          */
+       KRCN_VALUES_F32_EXACT = 2 };/* fp32 only if every value of the CSR survives the
+                                      round trip double(float(v)) == v, else FULL       */
+
 /* Formats reported by krcn_csr_plan_format. */
 enum { KRCN_PLAN_WAVE = 1, KRCN_PLAN_SORTED = 2, KRCN_PLAN_WINDOW_SLICES = 3, KRCN_PLAN_WINDOW_ACCUM = 4,
        KRCN_PLAN_JAG = 5, KRCN_PLAN_DENSE = 6 };
@@ -183,6 +219,14 @@ krcn_status krcn_csr_set_format(krcn_csr* h, int format);
 /* Tile format policy of one pass (1: X, 2: X^T), overriding krcn_csr_set_format
  * for it; -1 returns the pass to the handle's policy. */
 krcn_status krcn_csr_set_pass_format(krcn_csr* h, int pass, int format);
+/* Stored width of the plans' matrix values (KRCN_VALUES_*; see there).
+ * Invalidates the plans as krcn_csr_set_format does.  An unknown value is
+ * KRCN_ERR_INVALID; on a sharded handle a value other than KRCN_VALUES_FULL is
+ * KRCN_ERR_UNSUPPORTED; the handle is unchanged in both cases. */
+krcn_status krcn_csr_set_value_storage(krcn_csr* h, int values);
+/* Bytes per stored matrix value of each pass's plan (builds the plans if
+ * needed): out2_host = {pass 1, pass 2}. */
+krcn_status krcn_csr_plan_value_bytes(krcn_csr* h, int* out2_host);
 /* Execution plan summary (builds the plan if needed):
  * out8_host = {slices, lanes, tiles, grid} of pass 1 (X) then pass 2 (X^T);
  * a sorted-tile pass reports its slice count negated; a dense pass reports

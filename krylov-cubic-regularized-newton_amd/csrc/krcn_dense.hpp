@@ -22,6 +22,14 @@
 // order.  L = 1 with S = 1 is one left-to-right sum per row: scipy's
 // csr_matvec order for finite vectors (the stored zeros add +-0, which changes
 // no sum that starts from +0).
+//
+// Stored width (krcn_csr_set_value_storage).  The image's values have a stored
+// type TS of their own: the arithmetic type T, or float under T = double
+// (KRCN_VALUES_F32).  A narrowed image holds static_cast<float>(v) and has the
+// geometry of an fp32 image (four entries per 16-byte vector); the kernel
+// widens each stored value to double, which is exact, so vectors, products and
+// sums stay fp64 and the pass computes with double(float(A)).  The order above
+// holds with four entries per vector.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -33,6 +41,13 @@ namespace krcn {
 constexpr int kDenseNT = 256;        // threads per block (= kNT)
 constexpr int kDenseU = 8;           // 16-byte matrix loads in flight per lane: a wave holds 8 KiB, and the
                                      // >= 4 waves a CU runs reach the ~32 KiB that keep HBM streaming
+// ... under fp32 values and fp64 arithmetic (KRCN_VALUES_F32), where a matrix vector brings two 16-byte
+// loads of the gathered vector with it: 12 loads in flight per lane.  gisette, us per HVP / Lanczos call:
+// 41.3 / 517 at 4, 45.1 / 621 at 5, 52.8 / 661 at 8 (-DKRCN_DENSE_U_NARROW=...: the A/B of DESIGN.md §11)
+#ifndef KRCN_DENSE_U_NARROW
+#define KRCN_DENSE_U_NARROW 4
+#endif
+constexpr int kDenseUNarrow = KRCN_DENSE_U_NARROW;
 constexpr int kDenseLaneVecs = 4;    // AUTO lanes: the smallest L that leaves a lane <= this many vectors
 #if defined(KRCN_DENSE_LDS) && KRCN_DENSE_LDS
 constexpr int kDenseMaxGrid = 768;   // LDS-staging A/B build: 3 blocks per CU, each stages its slice of x once
@@ -45,7 +60,7 @@ constexpr int64_t kDenseSliceVecs = 256;  // ... while a slice keeps >= 4 KiB of
 
 // Geometry of one dense pass over a rows x cols matrix.
 struct DenseGeom {
-  int64_t ld = 0;      // entries per image row (a multiple of 16 / sizeof(T), >= cols)
+  int64_t ld = 0;      // entries per image row (a multiple of 16 / vs, vs the stored bytes per value; >= cols)
   int64_t nvec = 0;    // 16-byte vectors per row
   int L = 1, S = 1;    // lanes per row, column slices
   int64_t width = 0;   // entries of the widest slice (whole vectors; S * width >= cols)
@@ -145,28 +160,41 @@ struct DenseArgs {
   const void* mat;
 };
 
-// Entries [c, c + VW) of the gathered vector x (cols entries, any alignment):
-// one 16-byte load where the vector is whole and x is 16-byte aligned (c is a
-// multiple of VW), guarded scalar loads otherwise — x is never read at or
-// past cols (the image's padding multiplies zeros).
-template <typename T>
+// Entries [c, c + VW) of the gathered vector x (cols entries, any alignment),
+// VW the entries of one 16-byte vector of the stored type TS: 16-byte loads
+// (one when TS = T, two for fp32 values under fp64 arithmetic) where the vector
+// is whole and x is 16-byte aligned (c is a multiple of VW), guarded scalar
+// loads otherwise — x is never read at or past cols (the image's padding
+// multiplies zeros).
+template <typename T, typename TS>
 __device__ __forceinline__ void dense_x(const T* __restrict__ x, int64_t c, int64_t cols, bool aligned,
-                                        T (&o)[DenseVec<T>::VW]) {
+                                        T (&o)[DenseVec<TS>::VW]) {
   using DV = DenseVec<T>;
-  if (aligned && c + DV::VW <= cols) {
-    DV::unpack(*reinterpret_cast<const typename DV::V*>(x + c), o);
+  constexpr int VW = DenseVec<TS>::VW;
+  if (aligned && c + VW <= cols) {
+#pragma unroll
+    for (int q = 0; q < VW / DV::VW; ++q) {
+      T part[DV::VW];
+      DV::unpack(*reinterpret_cast<const typename DV::V*>(x + c + q * DV::VW), part);
+#pragma unroll
+      for (int e = 0; e < DV::VW; ++e) o[q * DV::VW + e] = part[e];
+    }
   } else {
 #pragma unroll
-    for (int e = 0; e < DV::VW; ++e) o[e] = c + e < cols ? x[c + e] : T(0);
+    for (int e = 0; e < VW; ++e) o[e] = c + e < cols ? x[c + e] : T(0);
   }
 }
 
-template <typename T, int L, class Src, class Epi>
+// T: the arithmetic type (vectors, products, sums); TS: the stored type of the
+// image (T itself, or float under T = double: KRCN_VALUES_F32, each stored
+// value widened to double, which is exact, before its fp64 product).
+template <typename T, typename TS, int L, class Src, class Epi>
 __global__ __launch_bounds__(kDenseNT) void k_dense_pass(DenseArgs a, Src src, Epi epi,
                                                          double* __restrict__ partials) {
-  using DV = DenseVec<T>;
+  using DV = DenseVec<TS>;
   using V = typename DV::V;
   constexpr int VW = DV::VW;
+  constexpr int kU = sizeof(TS) == sizeof(T) ? kDenseU : kDenseUNarrow;
   constexpr int kRowsPerWave = 64 / L, kRowsPerBlock = kDenseNT / L;
   __shared__ double sm[kDenseNT / 64];
   if constexpr (HasPreload<Src>::value) src.preload();
@@ -183,13 +211,13 @@ __global__ __launch_bounds__(kDenseNT) void k_dense_pass(DenseArgs a, Src src, E
 #if KRCN_DENSE_LDS
   // the slice of x as whole vectors in LDS (zeros past cols), read back with the matrix's vector indices
   __shared__ __attribute__((aligned(16))) T xs[kDenseLdsBytes / sizeof(T)];
-  const bool staged = int64_t(nv) * 16 <= kDenseLdsBytes;
+  const bool staged = int64_t(nv) * VW * int64_t(sizeof(T)) <= kDenseLdsBytes;
   if (staged) {
     for (int i = threadIdx.x; i < nv * VW; i += kDenseNT) xs[i] = c0 + i < a.cols ? x[c0 + i] : T(0);
     __syncthreads();
   }
 #endif
-  const T* __restrict__ mat = static_cast<const T*>(a.mat);
+  const TS* __restrict__ mat = static_cast<const TS*>(a.mat);
   typename RedOf<Epi>::type acc{};
   const int gstride = gridDim.x / a.S;
   for (int rg = blockIdx.x / a.S; rg < a.groups; rg += gstride) {
@@ -201,32 +229,32 @@ __global__ __launch_bounds__(kDenseNT) void k_dense_pass(DenseArgs a, Src src, E
     T s = T(0);
     if (live) {
       const V* __restrict__ row = reinterpret_cast<const V*>(mat + r64 * a.ld + c0);
-      for (int k = sub; k < nv; k += L * kDenseU) {
-        V m[kDenseU];
-        T xv[kDenseU][VW];
+      for (int k = sub; k < nv; k += L * kU) {
+        V m[kU];
+        T xv[kU][VW];
 #pragma unroll
-        for (int u = 0; u < kDenseU; ++u) {
+        for (int u = 0; u < kU; ++u) {
           const int i = k + u * L;
           m[u] = KRCN_DENSE_LOAD(row + (i < nv ? i : k));
         }
 #pragma unroll
-        for (int u = 0; u < kDenseU; ++u) {
+        for (int u = 0; u < kU; ++u) {
           const int i = k + u * L;
           if (i < nv) {
 #if KRCN_DENSE_LDS
-            if (staged) DV::unpack(*reinterpret_cast<const V*>(xs + int64_t(i) * VW), xv[u]);
+            if (staged) dense_x<T, TS>(xs, int64_t(i) * VW, int64_t(nv) * VW, true, xv[u]);
             else
 #endif
-            dense_x<T>(x, c0 + int64_t(i) * VW, a.cols, aligned, xv[u]);
+            dense_x<T, TS>(x, c0 + int64_t(i) * VW, a.cols, aligned, xv[u]);
           }
         }
 #pragma unroll
-        for (int u = 0; u < kDenseU; ++u) {
+        for (int u = 0; u < kU; ++u) {
           if (k + u * L < nv) {
-            T mv[VW];
+            TS mv[VW];
             DV::unpack(m[u], mv);
 #pragma unroll
-            for (int e = 0; e < VW; ++e) s += mv[e] * xv[u][e];
+            for (int e = 0; e < VW; ++e) s += T(mv[e]) * xv[u][e];
           }
         }
       }
@@ -245,16 +273,17 @@ __global__ __launch_bounds__(kDenseNT) void k_dense_pass(DenseArgs a, Src src, E
 // Image build: img[r * ld + idx[e]] = val[e] over the CSR's nonzeros, one wave
 // per row (the image is zero-filled first; a repeated entry would keep one of
 // its values, not their sum — unsupported, as elsewhere in the library).
-template <typename T>
+// TS: the stored type (a narrowed image rounds each value to nearest even).
+template <typename T, typename TS>
 __global__ __launch_bounds__(kDenseNT) void k_dense_scatter(int rows, const int* __restrict__ ptr,
                                                             const int* __restrict__ idx, const T* __restrict__ val,
-                                                            int64_t ld, T* __restrict__ img) {
+                                                            int64_t ld, TS* __restrict__ img) {
   const int lane = threadIdx.x & 63;
   const int64_t w0 = int64_t(blockIdx.x) * (kDenseNT / 64) + (threadIdx.x >> 6);
   const int64_t nw = int64_t(gridDim.x) * (kDenseNT / 64);
   for (int64_t r = w0; r < rows; r += nw) {
     const int b = ptr[r], e = ptr[r + 1];
-    for (int p = b + lane; p < e; p += 64) img[r * ld + idx[p]] = val[p];
+    for (int p = b + lane; p < e; p += 64) img[r * ld + idx[p]] = static_cast<TS>(val[p]);
   }
 }
 

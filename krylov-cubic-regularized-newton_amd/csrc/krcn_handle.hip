@@ -305,6 +305,28 @@ extern "C" krcn_status krcn_csr_set_pass_format(krcn_csr* h, int pass, int forma
   return KRCN_OK;
 }
 
+extern "C" krcn_status krcn_csr_set_value_storage(krcn_csr* h, int values) {
+  if (!h) return fail(KRCN_ERR_INVALID, "krcn_csr_set_value_storage: null handle");
+  if (values < KRCN_VALUES_FULL || values > KRCN_VALUES_F32_EXACT)
+    return fail(KRCN_ERR_INVALID, "krcn_csr_set_value_storage: expected 0 (full), 1 (f32) or 2 (f32 if exact)");
+  if (values != KRCN_VALUES_FULL && h->shard != KRCN_SHARD_NONE)
+    return fail(KRCN_ERR_UNSUPPORTED, "krcn_csr_set_value_storage: narrowed values do not run on a sharded handle");
+  if (h->values != values) {
+    h->values = values;
+    h->plans_ready = false;
+  }
+  return KRCN_OK;
+}
+
+extern "C" krcn_status krcn_csr_plan_value_bytes(krcn_csr* h, int* out2_host) {
+  if (!h || !out2_host) return fail(KRCN_ERR_INVALID, "krcn_csr_plan_value_bytes: null argument");
+  CHK(set_device(h));
+  CHK(ensure_plans(h));
+  const PassPlan* ps[2] = {&h->p1, &h->p2};
+  for (int i = 0; i < 2; ++i) out2_host[i] = ps[i]->dense ? ps[i]->dvs : int(h->vs);
+  return KRCN_OK;
+}
+
 extern "C" krcn_status krcn_csr_set_placement_trials(krcn_csr* h, int trials) {
   if (!h) return fail(KRCN_ERR_INVALID, "krcn_csr_set_placement_trials: null handle");
   if (trials < -1 || trials > krcn_csr::kPlaceMax)

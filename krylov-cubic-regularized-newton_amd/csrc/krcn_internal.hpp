@@ -265,6 +265,7 @@ struct PlanFields {
   void* xpart = nullptr;      //   per block X^T u partials (grid x cols)
   int dense = 0;              // dense format (k_dense_pass; S, L, grid, ntiles = row groups, own_val = the image)
   int64_t dld = 0;            //   entries per image row
+  int dvs = 0;                //   bytes per stored image value (sizeof(T), or 4 under KRCN_VALUES_F32)
   int64_t pcap = 0;           // entries of the handle's partials buffers (ensure_plans)
 };
 // ... and the owner of every device buffer those fields point to.
@@ -288,6 +289,8 @@ struct krcn_csr {
   int slicing = KRCN_SLICING_AUTO;
   int format = KRCN_FORMAT_AUTO;
   int format_pass[2] = {-1, -1};   // krcn_csr_set_pass_format (-1: the handle's format)
+  int values = KRCN_VALUES_FULL;   // krcn_csr_set_value_storage: stored width of the dense images' values
+  size_t dense_vs = 8;             //   bytes per stored value the current plan build decided on (build_plans)
   int sort_nt = 0;            // sorted-tile block size; 0 = by matrix size
   bool plans_ready = false;
   bool p1_unsliced = false;   // pass 2 took a single-window jagged plan: pass 1's sorted tiles go
@@ -575,18 +578,26 @@ inline krcn_status run_pass(PassPlan& P, const Src& first, const Src2& rest, con
     if constexpr (IsLzZ<Src>::value || IsLzU<Src>::value) {
       return fail(KRCN_ERR_UNSUPPORTED, "fused Lanczos steps do not run over a dense plan");
     } else {
-      DenseArgs da{P.rows, P.S, P.ntiles, P.cols, P.dld, P.dld / int64_t(16 / sizeof(T)), P.val};
-      with_lanes(P.L, [&](auto lc) {
-        constexpr int LL = decltype(lc)::value;
-        if (P.S == 1) {
-          hipLaunchKernelGGL((k_dense_pass<T, LL, Src, Epi>), dim3(P.grid), dim3(kDenseNT), 0, s, da, first, epi,
-                             partials);
-        } else {
-          EpiSlicePart<T> ep{static_cast<T*>(P.part), int64_t(P.rows)};
-          hipLaunchKernelGGL((k_dense_pass<T, LL, Src, EpiSlicePart<T>>), dim3(P.grid), dim3(kDenseNT), 0, s, da,
-                             first, ep, static_cast<double*>(nullptr));
-        }
-      });
+      if (P.dvs != int(sizeof(T)) && P.dvs != 4)
+        return fail(KRCN_ERR_INVALID, "run_pass: a dense plan with %d-byte values under %d-byte arithmetic", P.dvs,
+                    int(sizeof(T)));
+      DenseArgs da{P.rows, P.S, P.ntiles, P.cols, P.dld, P.dld / int64_t(16 / P.dvs), P.val};
+      auto launch = [&](auto ts) {   // ts: a value of the image's stored type
+        using TS = decltype(ts);
+        with_lanes(P.L, [&](auto lc) {
+          constexpr int LL = decltype(lc)::value;
+          if (P.S == 1) {
+            hipLaunchKernelGGL((k_dense_pass<T, TS, LL, Src, Epi>), dim3(P.grid), dim3(kDenseNT), 0, s, da, first,
+                               epi, partials);
+          } else {
+            EpiSlicePart<T> ep{static_cast<T*>(P.part), int64_t(P.rows)};
+            hipLaunchKernelGGL((k_dense_pass<T, TS, LL, Src, EpiSlicePart<T>>), dim3(P.grid), dim3(kDenseNT), 0, s,
+                               da, first, ep, static_cast<double*>(nullptr));
+          }
+        });
+      };
+      if (P.dvs == int(sizeof(T))) launch(T(0));
+      else launch(0.0f);   // fp32 values under fp64 arithmetic (KRCN_VALUES_F32)
       LAUNCHCHK();
       if (mid && P.S > 1) {
         HIPCHK(hipEventRecord(mid->em, s));

@@ -1006,28 +1006,73 @@ static krcn_status build_jag(PassPlan& P, const int* ptr, const int* idx, const 
 // ----------------------------------------------------------- dense format
 // The image of one pass (krcn_dense.hpp): zero fill plus a scatter of the CSR
 // on the build stream; the slice partials when the geometry slices the pass.
-template <typename T>
-static krcn_status build_dense(PassPlan& P, const int* ptr, const int* idx, const T* val, int lanes, int slicing,
-                               hipStream_t s) {
-  const DenseGeom g = dense_geometry(P.rows, P.cols, sizeof(T), lanes, slicing);
+// TS is the stored type of the image's values: T, or float on an fp64 handle
+// under KRCN_VALUES_F32 (the geometry is then that of an fp32 image).
+template <typename T, typename TS>
+static krcn_status build_dense_as(PassPlan& P, const int* ptr, const int* idx, const T* val, int lanes, int slicing,
+                                  hipStream_t s) {
+  const DenseGeom g = dense_geometry(P.rows, P.cols, sizeof(TS), lanes, slicing);
   CHK(P.own.alloc(&P.own_val, size_t(g.bytes)));
   HIPCHK(hipMemsetAsync(P.own_val, 0, size_t(g.bytes), s));
   if (P.nnz > 0) {
     const int64_t blocks = (int64_t(P.rows) + kDenseNT / 64 - 1) / (kDenseNT / 64);
-    hipLaunchKernelGGL((k_dense_scatter<T>), dim3(unsigned(std::min<int64_t>(blocks, 65536))), dim3(kDenseNT), 0, s,
-                       P.rows, ptr, idx, val, g.ld, static_cast<T*>(P.own_val));
+    hipLaunchKernelGGL((k_dense_scatter<T, TS>), dim3(unsigned(std::min<int64_t>(blocks, 65536))), dim3(kDenseNT), 0,
+                       s, P.rows, ptr, idx, val, g.ld, static_cast<TS*>(P.own_val));
     LAUNCHCHK();
   }
   if (g.S > 1) CHK(P.own.alloc(&P.part, sizeof(T) * size_t(g.S) * size_t(std::max(P.rows, 1))));
   HIPCHK(hipStreamSynchronize(s));
   P.dense = 1;
   P.dld = g.ld;
+  P.dvs = int(sizeof(TS));
   P.S = g.S;
   P.L = g.L;
   P.ntiles = int(g.groups);
   P.grid = g.grid;
   P.combine_grid = combine_grid(P.rows);
   P.val = P.own_val;
+  return KRCN_OK;
+}
+
+template <typename T>
+static krcn_status build_dense(PassPlan& P, const int* ptr, const int* idx, const T* val, int lanes, int slicing,
+                               size_t vs, hipStream_t s) {
+  if (vs == sizeof(T)) return build_dense_as<T, T>(P, ptr, idx, val, lanes, slicing, s);
+  return build_dense_as<T, float>(P, ptr, idx, val, lanes, slicing, s);
+}
+
+// KRCN_VALUES_F32_EXACT: *flag |= 1 when some value does not survive the round
+// trip through fp32 (a NaN never does).
+__global__ __launch_bounds__(256) void k_values_f32_exact(const double* __restrict__ val, int64_t nnz,
+                                                          int* __restrict__ flag) {
+  bool bad = false;
+  for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < nnz; i += int64_t(gridDim.x) * blockDim.x) {
+    const double v = val[i];
+    bad |= !(double(static_cast<float>(v)) == v);
+  }
+  if (bad) atomicOr(flag, 1);
+}
+
+// Bytes per stored value of the dense images a plan build is about to make:
+// the handle's policy (krcn_csr_set_value_storage), decided once per build.
+template <typename T>
+static krcn_status dense_value_bytes(const krcn_csr* h, hipStream_t s, size_t* vs) {
+  *vs = sizeof(T);
+  if (sizeof(T) == 4 || h->values == KRCN_VALUES_FULL) return KRCN_OK;
+  if (h->values == KRCN_VALUES_F32_EXACT && h->nnz > 0) {
+    DevTmp<int> flag;
+    CHK(flag.alloc(sizeof(int)));
+    HIPCHK(hipMemsetAsync(flag.p, 0, sizeof(int), s));
+    const int64_t blocks = (h->nnz + 255) / 256;
+    hipLaunchKernelGGL(k_values_f32_exact, dim3(unsigned(std::min<int64_t>(blocks, 4096))), dim3(256), 0, s,
+                       static_cast<const double*>(h->val), h->nnz, flag.p);
+    LAUNCHCHK();
+    int bad = 0;
+    HIPCHK(hipMemcpyAsync(&bad, flag.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (bad) return KRCN_OK;
+  }
+  *vs = 4;
   return KRCN_OK;
 }
 
@@ -1075,7 +1120,7 @@ static krcn_status build_plan(krcn_csr* h, int pass, int rows, int64_t cols, int
   if (fmt == KRCN_FORMAT_DENSE) {
     if (h->shard != KRCN_SHARD_NONE)
       return fail(KRCN_ERR_UNSUPPORTED, "the dense format does not run on a sharded handle");
-    return build_dense<T>(P, ptr, idx, val, lanes, h->slicing, s);
+    return build_dense<T>(P, ptr, idx, val, lanes, h->slicing, h->dense_vs, s);
   }
   // jagged format: forced, or by the auto policy (its summation order is
   // scipy's, so the sequential lane policy may use it too)
@@ -1194,8 +1239,9 @@ static krcn_status build_plans(krcn_csr* h, bool lz2, hipStream_t s) {
   {
     const bool dn[2] = {pass_format(h, 1) == KRCN_FORMAT_DENSE, pass_format(h, 2) == KRCN_FORMAT_DENSE};
     if ((dn[0] || dn[1]) && h->shard == KRCN_SHARD_NONE) {
-      const int64_t b1 = dn[0] ? dense_geometry(h->n, h->d, sizeof(T), h->lanes_x, h->slicing).bytes : 0;
-      const int64_t b2 = dn[1] ? dense_geometry(h->d, h->n, sizeof(T), h->lanes_xt, h->slicing).bytes : 0;
+      CHK(dense_value_bytes<T>(h, s, &h->dense_vs));   // (the stored width: the images are sized by it)
+      const int64_t b1 = dn[0] ? dense_geometry(h->n, h->d, h->dense_vs, h->lanes_x, h->slicing).bytes : 0;
+      const int64_t b2 = dn[1] ? dense_geometry(h->d, h->n, h->dense_vs, h->lanes_xt, h->slicing).bytes : 0;
       const int64_t need = b1 > INT64_MAX - b2 ? INT64_MAX : b1 + b2;
       size_t mfree = 0, mtotal = 0;
       HIPCHK(hipMemGetInfo(&mfree, &mtotal));

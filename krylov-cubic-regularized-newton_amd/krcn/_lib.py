@@ -24,6 +24,7 @@ KRCN_LANES_AUTO, KRCN_LANES_SEQUENTIAL = 0, 1
 KRCN_SLICING_AUTO, KRCN_SLICING_OFF = 0, 1
 KRCN_FORMAT_AUTO, KRCN_FORMAT_WAVE, KRCN_FORMAT_SORTED, KRCN_FORMAT_WINDOW, KRCN_FORMAT_JAG = 0, 1, 2, 3, 4
 KRCN_FORMAT_DENSE = 5
+KRCN_VALUES_FULL, KRCN_VALUES_F32, KRCN_VALUES_F32_EXACT = 0, 1, 2
 KRCN_PLAN_WAVE, KRCN_PLAN_SORTED, KRCN_PLAN_WINDOW_SLICES, KRCN_PLAN_WINDOW_ACCUM = 1, 2, 3, 4
 KRCN_PLAN_JAG, KRCN_PLAN_DENSE = 5, 6
 KRCN_SPACE_N, KRCN_SPACE_D = 0, 1
@@ -69,6 +70,8 @@ SIGNATURES = {
     "krcn_csr_set_slicing": [_vp, _i],
     "krcn_csr_set_format": [_vp, _i],
     "krcn_csr_set_pass_format": [_vp, _i, _i],
+    "krcn_csr_set_value_storage": [_vp, _i],
+    "krcn_csr_plan_value_bytes": [_vp, ctypes.POINTER(ctypes.c_int)],
     "krcn_csr_set_graph": [_vp, _i],
     "krcn_csr_set_placement_trials": [_vp, _i],
     "krcn_csr_placement_info": [_vp, _dp],

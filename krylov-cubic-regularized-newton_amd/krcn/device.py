@@ -37,7 +37,8 @@ class DeviceCSR:
     """
 
     def __init__(self, A, device=None, dtype=torch.float64, n_global=None,
-                 shard_mode=_lib.KRCN_SHARD_NONE, lanes=(0, 0), slicing=0, fmt=0, pass_formats=None):
+                 shard_mode=_lib.KRCN_SHARD_NONE, lanes=(0, 0), slicing=0, fmt=0, pass_formats=None,
+                 values=0):
         if not torch.cuda.is_available():
             raise RuntimeError("krcn.DeviceCSR needs a HIP device (no CPU fallback exists)")
         if dtype not in _DTYPES:
@@ -73,6 +74,7 @@ class DeviceCSR:
         if pass_formats is not None:
             for k, f in enumerate(pass_formats):
                 self.set_pass_format(k + 1, f)
+        self.set_value_storage(values)
 
     # -- lifecycle ---------------------------------------------------------
     def close(self):
@@ -115,6 +117,25 @@ class DeviceCSR:
         """Tile format of one pass (1: X, 2: X^T), overriding set_format for it; -1 restores it."""
         call("krcn_csr_set_pass_format", self._h, int(pass_), int(fmt))
         self._replan()
+
+    _VALUES = {"full": _lib.KRCN_VALUES_FULL, "f32": _lib.KRCN_VALUES_F32, "f32-exact": _lib.KRCN_VALUES_F32_EXACT}
+
+    def set_value_storage(self, values=0):
+        """Stored width of the dense images' values: "full" / 0 the handle's dtype, "f32" / 1 fp32 (each
+        value rounded; arithmetic, vectors and sums keep the dtype), "f32-exact" / 2 fp32 only if no
+        value of the matrix changes by it.  CSR-format passes keep full width."""
+        if isinstance(values, str):
+            if values not in self._VALUES:
+                raise ValueError(f'values must be "full", "f32" or "f32-exact", got {values!r}')
+            values = self._VALUES[values]
+        call("krcn_csr_set_value_storage", self._h, int(values))
+        self._replan()
+
+    def plan_value_bytes(self):
+        """{'pass1': bytes, 'pass2': bytes} per stored matrix value of each pass's plan."""
+        buf = (ctypes.c_int * 2)()
+        call("krcn_csr_plan_value_bytes", self._h, buf)
+        return {"pass1": int(buf[0]), "pass2": int(buf[1])}
 
     def _multi_rank(self):
         return self._comm is not None and getattr(self._comm, "world", 1) > 1

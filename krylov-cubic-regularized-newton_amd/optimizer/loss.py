@@ -122,10 +122,14 @@ class LogisticRegression(Oracle):
     format: None keeps the handle's format policy, "dense" stores A and A^T as
     row-major images without indices (nearly dense A such as gisette, madelon
     or duke; unsharded only), an int is a KRCN_FORMAT_* value.
+    values: with format="dense" only, "f32" stores the images' values in fp32
+    (each rounded; vectors, sums and the recurrence keep the dtype, the matrix
+    bytes of an fp64 pass halve) and "f32-exact" does so only if no value of A
+    changes by it; None or "full" keeps the dtype.
     """
 
     def __init__(self, A, b, store_mat_vec_prod=False, *args, device=None, dtype=torch.float64,
-                 shard=None, lanes=(0, 0), format=None, **kwargs):
+                 shard=None, lanes=(0, 0), format=None, values=None, **kwargs):
         super().__init__(*args, **kwargs)
         if format is None or (isinstance(format, (int, np.integer)) and not isinstance(format, bool)):
             fmt = None if format is None else int(format)
@@ -133,6 +137,10 @@ class LogisticRegression(Oracle):
             fmt = _lib.KRCN_FORMAT_DENSE
         else:
             raise ValueError(f"format must be None, 'dense' or a KRCN_FORMAT_* int, got {format!r}")
+        if values not in (None, "full", "f32", "f32-exact"):
+            raise ValueError(f"values must be None, 'full', 'f32' or 'f32-exact', got {values!r}")
+        if values not in (None, "full") and fmt != _lib.KRCN_FORMAT_DENSE:
+            raise ValueError(f"values={values!r} needs format='dense': only dense passes store narrowed values")
         import scipy.sparse as sp
         self.A = A
         self.b = _labels01(b)
@@ -147,6 +155,8 @@ class LogisticRegression(Oracle):
                                             n_global=self.n, shard_mode=mode, lanes=lanes)
         if fmt is not None:
             self.device_matrix.set_format(fmt)
+        if values not in (None, "full"):
+            self.device_matrix.set_value_storage(values)
         if shard is not None and shard.comm is not None:
             self.device_matrix.attach_comm(shard.comm)
         if fmt == _lib.KRCN_FORMAT_DENSE:
