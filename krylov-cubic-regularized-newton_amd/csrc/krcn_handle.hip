@@ -119,7 +119,10 @@ extern "C" krcn_status krcn_csr_create(int device, int64_t n, int64_t d, int64_t
                 (long long)n, (long long)d);
   if (n_global <= 0) n_global = n;
   krcn_csr* h = new krcn_csr();
-  if (const char* e = tuning_env("KRCN_SORT_NT")) h->sort_nt = atoi(e) == 256 || atoi(e) == 512 || atoi(e) == 1024 ? atoi(e) : 0;  // tuning knob
+  {
+    const int nt = tuning_value("KRCN_SORT_NT", 0);   // tuning knob
+    if (nt == 256 || nt == 512 || nt == 1024) h->sort_nt = nt;
+  }
   h->device = device;
   h->dtype = dtype;
   h->vs = dtype == KRCN_F64 ? 8 : 4;
@@ -323,7 +326,7 @@ extern "C" krcn_status krcn_csr_plan_value_bytes(krcn_csr* h, int* out2_host) {
   CHK(set_device(h));
   CHK(ensure_plans(h));
   const PassPlan* ps[2] = {&h->p1, &h->p2};
-  for (int i = 0; i < 2; ++i) out2_host[i] = ps[i]->dense ? ps[i]->dvs : int(h->vs);
+  for (int i = 0; i < 2; ++i) out2_host[i] = ps[i]->kind == KRCN_PLAN_DENSE ? ps[i]->dvs : int(h->vs);
   return KRCN_OK;
 }
 
@@ -369,7 +372,7 @@ extern "C" krcn_status krcn_csr_plan_info(krcn_csr* h, int* out8_host) {
   CHK(ensure_plans(h));
   const PassPlan* ps[2] = {&h->p1, &h->p2};
   for (int i = 0; i < 2; ++i) {
-    out8_host[4 * i + 0] = ps[i]->sorted ? -ps[i]->S : ps[i]->S;
+    out8_host[4 * i + 0] = ps[i]->kind == KRCN_PLAN_SORTED ? -ps[i]->S : ps[i]->S;
     out8_host[4 * i + 1] = ps[i]->L;
     out8_host[4 * i + 2] = ps[i]->ntiles;
     out8_host[4 * i + 3] = ps[i]->grid;
@@ -381,12 +384,8 @@ extern "C" krcn_status krcn_csr_plan_format(krcn_csr* h, int* out2_host) {
   if (!h || !out2_host) return fail(KRCN_ERR_INVALID, "krcn_csr_plan_format: null argument");
   CHK(set_device(h));
   CHK(ensure_plans(h));
-  const PassPlan* ps[2] = {&h->p1, &h->p2};
-  for (int i = 0; i < 2; ++i)
-    out2_host[i] = ps[i]->dense ? KRCN_PLAN_DENSE
-                   : ps[i]->jag ? KRCN_PLAN_JAG
-                   : ps[i]->win ? (ps[i]->accum ? KRCN_PLAN_WINDOW_ACCUM : KRCN_PLAN_WINDOW_SLICES)
-                   : ps[i]->sorted ? KRCN_PLAN_SORTED : KRCN_PLAN_WAVE;
+  out2_host[0] = h->p1.kind;
+  out2_host[1] = h->p2.kind;
   return KRCN_OK;
 }
 

@@ -9,8 +9,10 @@
 //   krcn_coord.hip       coordinate blocks of SSCN (gradient, Hessian block, Ax update)
 //   krcn_lanczos_f64.hip / krcn_lanczos_f32.hip
 //                        the device Lanczos recurrence (krcn_lanczos_impl.hpp), one dtype each
-// This header holds the handle layout, the error macros and the pass launcher
-// (run_pass) that the kernels of every unit are instantiated through.
+// This header holds the handle layout, the error macros and the host helpers;
+// it ends by including
+//   krcn_pass.hpp        the pass launcher (run_pass, run_combine, the shape of a pass) that the
+//                        kernels of every unit are instantiated through
 #pragma once
 #include "krcn.h"
 #include "krcn_host.hpp"
@@ -32,6 +34,7 @@
 #include <mutex>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <type_traits>
@@ -50,6 +53,25 @@ inline const char* tuning_env(const char* name) {
   return nullptr;
 #endif
 }
+// The three readings of a knob: a number (dflt when unset; V is int, int64_t
+// or double; field f of a comma-separated list), a switch that is on unless
+// set to 0, one that is off unless set to 1.  A site keeps the value in a
+// function-local static and checks its range.
+template <typename V>
+inline V tuning_value(const char* name, V dflt, int field = 0) {
+  const char* e = tuning_env(name);
+  for (; e && field > 0; --field)
+    if ((e = std::strchr(e, ',')) != nullptr) ++e;
+  return e ? V(std::atof(e)) : dflt;
+}
+inline bool tuning_on(const char* name) {
+  const char* e = tuning_env(name);
+  return !(e && e[0] == '0');
+}
+inline bool tuning_off(const char* name) {
+  const char* e = tuning_env(name);
+  return e && e[0] == '1';
+}
 
 // CGS2 colsweep shape (krcn_cgs2.hpp k_cgs_colsweep): rows per wave and batch
 // past k = 4 U (tuning knob KRCN_CGS_COLU) and batches per block (KRCN_CGS_NB);
@@ -57,15 +79,14 @@ inline const char* tuning_env(const char* name) {
 // count of a sweep over k rows sizes the row-range partials (reserve_reorth).
 inline int cgs_umax() {
   static const int v = [] {
-    const char* e = tuning_env("KRCN_CGS_COLU");
-    return e && std::atoi(e) >= 2 ? std::atoi(e) : 8;
+    const int x = tuning_value("KRCN_CGS_COLU", 8);
+    return x >= 2 ? x : 8;
   }();
   return v;
 }
 inline int cgs_nb() {
   static const int v = [] {
-    const char* e = tuning_env("KRCN_CGS_NB");
-    const int x = e ? std::atoi(e) : 8;
+    const int x = tuning_value("KRCN_CGS_NB", 8);
     return x == 1 || x == 2 || x == 4 || x == 16 ? x : 8;
   }();
   return v;
@@ -229,13 +250,13 @@ struct PlanFields {
   TileDesc* tiles = nullptr;
   int* tbeg = nullptr;        // groups + 1 tile offsets
   void* part = nullptr;       // S * rows partial row sums (sliced)
-  int sorted = 0;             // sorted block tiles (k_sorted_pass) instead of wave tiles
+  int kind = KRCN_PLAN_WAVE;  // the format (KRCN_PLAN_*): the one kernel family that runs the plan
+  // sorted block tiles (k_sorted_pass) instead of wave tiles
   int sort_nt = 256;          // sorted tiles: threads per block (tile = kSortPerThread x sort_nt nonzeros)
   unsigned* gword = nullptr;  // sorted tiles: (column - tile base) << kSortSlotBits | CSR slot
   void* gval = nullptr;       //               value, same (tile-sorted) order
   int* tmid = nullptr;        // sorted tiles: first single-long-row tile of each group
-  int win = 0;                // LDS-window format (k_window_pass)
-  int accum = 0;              //   1: every block walks all slices of its tile range (no partials)
+  // LDS-window formats (k_window_pass; window-accum: every block walks all slices of its tile range, no partials)
   int R = 64;                 //   rows per tile (one lane per row)
   int W = 0;                  //   slice width (window entries)
   int stride = 1;             //   segment slots per block
@@ -245,7 +266,7 @@ struct PlanFields {
   WinSeg* segs = nullptr;     // per-block segment lists: block b runs segs[b * stride + i]
   int* tb = nullptr;          // compact row pointers: tile bases (S x (ntiles + 1))
   unsigned short* ro = nullptr;   //   row ends relative to the tile base (S x rows)
-  int jag = 0;                // jagged lane-per-row format (k_jag_pass; S, W, widx, own_val, grid)
+  // jagged lane-per-row format (k_jag_pass; S, W, widx, own_val, grid)
   int jK = 0;                 //   groups per wave (units per wave and slice)
   int jG = 1, jSg = 1;        //   accumulate: slice groups, slices per group
   int* jgcut = nullptr;       //   group cuts per block (grid + 1)
@@ -263,7 +284,7 @@ struct PlanFields {
   unsigned short* xrow = nullptr;  //   row offsets in the block's rows, column-major per block
   void* xval = nullptr;
   void* xpart = nullptr;      //   per block X^T u partials (grid x cols)
-  int dense = 0;              // dense format (k_dense_pass; S, L, grid, ntiles = row groups, own_val = the image)
+  // dense format (k_dense_pass; S, L, grid, ntiles = row groups, own_val = the image)
   int64_t dld = 0;            //   entries per image row
   int dvs = 0;                //   bytes per stored image value (sizeof(T), or 4 under KRCN_VALUES_F32)
   int64_t pcap = 0;           // entries of the handle's partials buffers (ensure_plans)
@@ -427,28 +448,6 @@ inline int resolve_lanes(int policy, int64_t rows, int64_t nnz) {
   return policy;
 }
 
-template <typename F>
-inline void with_lanes(int L, F&& f) {
-  switch (L) {
-    case 1: f(std::integral_constant<int, 1>{}); break;
-    case 2: f(std::integral_constant<int, 2>{}); break;
-    case 4: f(std::integral_constant<int, 4>{}); break;
-    case 8: f(std::integral_constant<int, 8>{}); break;
-    case 16: f(std::integral_constant<int, 16>{}); break;
-    case 32: f(std::integral_constant<int, 32>{}); break;
-    default: f(std::integral_constant<int, 64>{}); break;
-  }
-}
-
-template <class F>
-inline void with_sort_nt(int nt, F&& f) {
-  switch (nt) {
-    case 512: f(std::integral_constant<int, 512>{}); break;
-    case 1024: f(std::integral_constant<int, 1024>{}); break;
-    default: f(std::integral_constant<int, 256>{}); break;
-  }
-}
-
 inline krcn_status set_device(const krcn_csr* h) {
   HIPCHK(hipSetDevice(h->device));
   return KRCN_OK;
@@ -494,350 +493,10 @@ inline ProfRec* prof_next(krcn_csr* h) {
   return r;
 }
 
-// A/B knob KRCN_COMBINE_W=1: slices combine with 16-byte loads (k_slice_combine_w).
-inline bool combine_w_env() {
-  static const bool v = [] {
-    const char* e = tuning_env("KRCN_COMBINE_W");
-    return e && e[0] == '1';
-  }();
-  return v;
-}
-
-// The slice combine of a sliced pass over its S partial arrays (P.part).
-template <typename T, class Src2, class Epi>
-inline krcn_status run_combine(PassPlan& P, int S, const Src2& rest, const Epi& epi, double* partials, int* Pout,
-                               hipStream_t s) {
-  int grid = P.combine_grid;
-  if (S <= kCombineSmallS) {
-    grid = combine_small_grid(P.rows);
-    const int nt = combine_small_nt(P.rows);
-    const T* pp = static_cast<const T*>(P.part);
-    auto go = [&](auto sm, auto ntc) {
-      hipLaunchKernelGGL((k_slice_combine_small<T, Src2, Epi, decltype(sm)::value, decltype(ntc)::value>), dim3(grid),
-                         dim3(decltype(ntc)::value), 0, s, P.rows, S, pp, rest, epi, partials);
-    };
-    auto by_s = [&](auto ntc) {
-      if (S <= 2) go(std::integral_constant<int, 2>{}, ntc);
-      else if (S <= 4) go(std::integral_constant<int, 4>{}, ntc);
-      else if (S <= 8) go(std::integral_constant<int, 8>{}, ntc);
-      else go(std::integral_constant<int, 16>{}, ntc);
-    };
-    if (nt == 256) by_s(std::integral_constant<int, 256>{});
-    else by_s(std::integral_constant<int, kCombineNT>{});
-  } else if (combine_w_env() && S >= 32 && P.rows % CombW<T>::VW == 0 &&
-             combine_w_grid(P.rows, CombW<T>::VW) <= P.pcap) {
-    grid = combine_w_grid(P.rows, CombW<T>::VW);
-    hipLaunchKernelGGL((k_slice_combine_w<T, Src2, Epi>), dim3(grid), dim3(kCombineNT), 0, s, P.rows, S,
-                       static_cast<const T*>(P.part), rest, epi, partials);
-  } else {
-    hipLaunchKernelGGL((k_slice_combine<T, Src2, Epi>), dim3(grid), dim3(kCombineNT), 0, s, P.rows, S,
-                       combine_rows(P.rows), static_cast<const T*>(P.part), rest, epi, partials);
-  }
-  LAUNCHCHK();
-  if (Pout) *Pout = grid;
-  return KRCN_OK;
-}
-
-// One SpMV pass: `first` is the source of the tiled launch, `rest` of the
-// slice-combine launch (sliced plans); partial sums of a reducing epilogue land
-// in `partials` (*Pout entries).
-// `mid` (profiling): its em event is recorded between the main launch and
-// the slice combine.
-template <typename T, class Src, class Src2, class Epi>
-inline krcn_status run_pass(PassPlan& P, const Src& first, const Src2& rest, const Epi& epi, double* partials,
-                            int* Pout, hipStream_t s, ProfRec* mid = nullptr) {
-  // a reducing launch writes one partial per block: the buffer must hold them
-  // (dense plans as wave tiles: the combine's grid when sliced, else the main launch's)
-  const int reducer_grid = P.jag ? (P.jG > 1 ? P.combine_grid : P.grid)
-                                 : (P.win ? !P.accum : P.S > 1) ? P.combine_grid : P.grid;
-  if (partials && reducer_grid > P.pcap)
-    return fail(KRCN_ERR_INVALID, "run_pass: %d partials exceed the %lld-entry buffer", reducer_grid,
-                (long long)P.pcap);
-  if constexpr (IsLzSmall<Src>::value) {   // one-piece window-accum plans only
-    if (!P.win || !P.accum || P.S != 1 || P.cols > kWinNT)
-      return fail(KRCN_ERR_UNSUPPORTED, "fused small-vector Lanczos pass 1 needs a one-piece window-accum plan");
-    WinArgs wa{P.rows, P.W, P.stride, P.S, 1, P.ntiles, P.cols, P.tb, P.ro, P.widx, P.val, P.segs};
-    wa.kpb = P.kpb;
-    if (P.R == 16)
-      hipLaunchKernelGGL((k_window_pass<T, 16, Src, Epi, true>), dim3(P.grid), dim3(kWinNT), 0, s, wa, first, epi,
-                         partials);
-    else if (P.R == 32)
-      hipLaunchKernelGGL((k_window_pass<T, 32, Src, Epi, true>), dim3(P.grid), dim3(kWinNT), 0, s, wa, first, epi,
-                         partials);
-    else
-      hipLaunchKernelGGL((k_window_pass<T, 64, Src, Epi, true>), dim3(P.grid), dim3(kWinNT), 0, s, wa, first, epi,
-                         partials);
-    LAUNCHCHK();
-    if (Pout) *Pout = P.grid;
-    return KRCN_OK;
-  } else {
-  if (P.dense) {
-    // dense plans run the generic step only: the sources of the fused steps
-    // are never selected for one (lanczos_impl: fuse, fuse_u and early need a
-    // window, sorted or jagged pass 1)
-    if constexpr (IsLzZ<Src>::value || IsLzU<Src>::value) {
-      return fail(KRCN_ERR_UNSUPPORTED, "fused Lanczos steps do not run over a dense plan");
-    } else {
-      if (P.dvs != int(sizeof(T)) && P.dvs != 4)
-        return fail(KRCN_ERR_INVALID, "run_pass: a dense plan with %d-byte values under %d-byte arithmetic", P.dvs,
-                    int(sizeof(T)));
-      DenseArgs da{P.rows, P.S, P.ntiles, P.cols, P.dld, P.dld / int64_t(16 / P.dvs), P.val};
-      auto launch = [&](auto ts) {   // ts: a value of the image's stored type
-        using TS = decltype(ts);
-        with_lanes(P.L, [&](auto lc) {
-          constexpr int LL = decltype(lc)::value;
-          if (P.S == 1) {
-            hipLaunchKernelGGL((k_dense_pass<T, TS, LL, Src, Epi>), dim3(P.grid), dim3(kDenseNT), 0, s, da, first,
-                               epi, partials);
-          } else {
-            EpiSlicePart<T> ep{static_cast<T*>(P.part), int64_t(P.rows)};
-            hipLaunchKernelGGL((k_dense_pass<T, TS, LL, Src, EpiSlicePart<T>>), dim3(P.grid), dim3(kDenseNT), 0, s,
-                               da, first, ep, static_cast<double*>(nullptr));
-          }
-        });
-      };
-      if (P.dvs == int(sizeof(T))) launch(T(0));
-      else launch(0.0f);   // fp32 values under fp64 arithmetic (KRCN_VALUES_F32)
-      LAUNCHCHK();
-      if (mid && P.S > 1) {
-        HIPCHK(hipEventRecord(mid->em, s));
-        mid->mid = true;
-      }
-      if (P.S > 1) {
-        CHK(run_combine<T>(P, P.S, rest, epi, partials, Pout, s));
-      } else if (Pout) {
-        *Pout = P.grid;
-      }
-      return KRCN_OK;
-    }
-  }
-  if constexpr (IsLzU<Src>::value) {
-    if (!P.jag || P.S != 1)
-      return fail(KRCN_ERR_UNSUPPORTED, "the two-launch Lanczos pass 2 needs a single-window jagged plan");
-  }
-  if (P.jag) {
-    if constexpr (IsLzZ<Src>::value) {
-      return fail(KRCN_ERR_UNSUPPORTED, "fused Lanczos pass 1 needs an LDS-window slices plan");
-    } else {
-      JagArgs ja{P.rows, P.S == 1 ? 1 : P.jSg, P.W, P.jG, P.cols, P.jgcut, P.jumeta, P.jcnt, P.widx, P.val};
-      ja.xmap = P.S == 1 && KRCN_JAG_XMAP;
-      if (P.jlong > 0) {
-        ja.nlong = P.jlong;
-        ja.lpiece = P.jlpiece;
-        ja.lcut = P.jlcut;
-        ja.tcut = P.jlcut + P.grid + 1;
-        ja.lrow = P.jlrow;
-        ja.ltask = P.jltask;
-        ja.task = P.jtask;
-        ja.lidx = P.jlidx;
-        ja.lval = P.jlval;
-      }
-      // accumulate over G slice groups: per-group partial row sums, combined
-      // in group order by k_slice_combine (which runs the epilogue)
-      auto acc = [&](const auto& ep, double* parts) {
-        using E = std::decay_t<decltype(ep)>;
-        if (P.jK == 4)
-          hipLaunchKernelGGL((k_jag_acc<T, 4, Src, E>), dim3(P.grid), dim3(kJagNT), 0, s, ja, first, ep, parts);
-        else
-          hipLaunchKernelGGL((k_jag_acc<T, kJagK2, Src, E>), dim3(P.grid), dim3(kJagNT), 0, s, ja, first, ep, parts);
-      };
-      if (P.S == 1) {
-        auto one = [&](auto kc) {
-          hipLaunchKernelGGL((k_jag_pass<T, decltype(kc)::value, jag_cpg(decltype(kc)::value), 8, Src, Epi>), dim3(P.grid), dim3(kJagNT),
-                             0, s, ja, first, epi, partials);
-        };
-        if (P.jK == 1) one(std::integral_constant<int, 1>{});
-        else if (P.jK == 2) one(std::integral_constant<int, 2>{});
-        else if (P.jK == 3) one(std::integral_constant<int, 3>{});
-        else one(std::integral_constant<int, kJagK1>{});
-      }
-      else if (P.jG > 1)
-        acc(EpiSlicePart<T>{static_cast<T*>(P.part), int64_t(P.rows)}, static_cast<double*>(nullptr));
-      else
-        acc(epi, partials);
-      LAUNCHCHK();
-      if (mid && P.S > 1 && P.jG > 1) {   // (events only where a combine launch follows)
-        HIPCHK(hipEventRecord(mid->em, s));
-        mid->mid = true;
-      }
-      if (P.S > 1 && P.jG > 1) {
-        CHK(run_combine<T>(P, P.jG, rest, epi, partials, Pout, s));
-      } else if (Pout) {
-        *Pout = P.grid;
-      }
-      return KRCN_OK;
-    }
-  }
-  if (P.win) {
-    WinArgs wa{P.rows, P.W, P.stride, P.S, IsLzZ<Src>::value ? 2 : (P.accum ? 1 : 0), P.ntiles, P.cols,
-                     P.tb, P.ro, P.widx, P.val, P.segs};
-    wa.kpb = P.kpb;
-    auto launch = [&](auto rc) {
-      constexpr int RR = decltype(rc)::value;
-      if constexpr (IsLzZ<Src>::value) {   // fused step B: slices-mode plans only
-        EpiSlicePart<T> ep{static_cast<T*>(P.part), int64_t(P.rows)};
-        hipLaunchKernelGGL((k_window_pass<T, RR, Src, EpiSlicePart<T>, false>), dim3(P.grid), dim3(kWinNT), 0, s,
-                           wa, first, ep, static_cast<double*>(nullptr));
-      } else if (P.accum) {
-        hipLaunchKernelGGL((k_window_pass<T, RR, Src, Epi, true>), dim3(P.grid), dim3(kWinNT), 0, s, wa, first, epi,
-                           partials);
-      } else {
-        EpiSlicePart<T> ep{static_cast<T*>(P.part), int64_t(P.rows)};
-        hipLaunchKernelGGL((k_window_pass<T, RR, Src, EpiSlicePart<T>, false>), dim3(P.grid), dim3(kWinNT), 0, s,
-                           wa, first, ep, static_cast<double*>(nullptr));
-      }
-    };
-    if (P.R == 16) launch(std::integral_constant<int, 16>{});
-    else if (P.R == 32) launch(std::integral_constant<int, 32>{});
-    else launch(std::integral_constant<int, 64>{});
-    LAUNCHCHK();
-    if (mid && !P.accum) {
-      HIPCHK(hipEventRecord(mid->em, s));
-      mid->mid = true;
-    }
-    if (!P.accum) {
-      CHK(run_combine<T>(P, P.S, rest, epi, partials, Pout, s));
-    } else if (Pout) {
-      *Pout = P.grid;
-    }
-    return KRCN_OK;
-  }
-  if constexpr (IsLzZ<Src>::value) {
-    if constexpr (std::is_same<Epi, EpiWeighted<T>>::value) {
-    if (!P.sorted || P.S != 1)
-      return fail(KRCN_ERR_UNSUPPORTED, "the two-launch Lanczos pass 1 needs an unsliced sorted-tile plan");
-    {
-      // unsliced: the two-launch step (pass 2's SrcLzU settles beta); epi is
-      // the caller's (EpiWeighted: u' = w (.) X z_j)
-      with_lanes(P.L, [&](auto lc) {
-        constexpr int LL = decltype(lc)::value;
-        with_sort_nt(P.sort_nt, [&](auto nc) {
-          constexpr int NT = decltype(nc)::value;
-          hipLaunchKernelGGL((k_sorted_pass<T, LL, NT, Src, Epi>), dim3(P.grid), dim3(NT), 0, s, P.rows, 1, P.ptr,
-                             P.gword, static_cast<const T*>(P.gval), P.tiles, P.tbeg, P.tmid, first, epi, partials);
-        });
-      });
-      LAUNCHCHK();
-      if (Pout) *Pout = P.grid;
-      return KRCN_OK;
-    }
-    } else {
-    // fused step B over sorted tiles, sliced: the combine settles beta
-    if (!P.sorted)
-      return fail(KRCN_ERR_UNSUPPORTED, "fused Lanczos pass 1 needs an LDS-window or sorted-tile plan");
-    with_lanes(P.L, [&](auto lc) {
-      constexpr int LL = decltype(lc)::value;
-      with_sort_nt(P.sort_nt, [&](auto nc) {
-        constexpr int NT = decltype(nc)::value;
-        EpiSlicePart<T> ep{static_cast<T*>(P.part), int64_t(P.rows)};
-        hipLaunchKernelGGL((k_sorted_pass<T, LL, NT, Src, EpiSlicePart<T>>), dim3(P.grid), dim3(NT), 0, s, P.rows,
-                           P.groups, P.ptr, P.gword, static_cast<const T*>(P.gval), P.tiles, P.tbeg, P.tmid, first,
-                           ep, static_cast<double*>(nullptr));
-      });
-    });
-    LAUNCHCHK();
-    if (mid) {
-      HIPCHK(hipEventRecord(mid->em, s));
-      mid->mid = true;
-    }
-    return run_combine<T>(P, P.S, rest, epi, partials, Pout, s);
-    }
-  } else {
-  with_lanes(P.L, [&](auto lc) {
-    constexpr int LL = decltype(lc)::value;
-    if (P.sorted) {
-      with_sort_nt(P.sort_nt, [&](auto nc) {
-        constexpr int NT = decltype(nc)::value;
-        if (P.S == 1) {
-          hipLaunchKernelGGL((k_sorted_pass<T, LL, NT, Src, Epi>), dim3(P.grid), dim3(NT), 0, s, P.rows, 1, P.ptr,
-                             P.gword, static_cast<const T*>(P.gval), P.tiles, P.tbeg, P.tmid, first, epi,
-                             partials);
-        } else {
-          EpiSlicePart<T> ep{static_cast<T*>(P.part), int64_t(P.rows)};
-          hipLaunchKernelGGL((k_sorted_pass<T, LL, NT, Src, EpiSlicePart<T>>), dim3(P.grid), dim3(NT), 0, s,
-                             P.rows, P.groups, P.ptr, P.gword, static_cast<const T*>(P.gval), P.tiles, P.tbeg,
-                             P.tmid, first, ep, static_cast<double*>(nullptr));
-        }
-      });
-    } else if (P.S == 1) {
-      hipLaunchKernelGGL((k_tiled_pass<T, LL, Src, Epi>), dim3(P.grid), dim3(kNT), 0, s, P.rows, 1, P.ptr, P.idx,
-                         static_cast<const T*>(P.val), P.tiles, P.tbeg, first, epi, partials);
-    } else {
-      EpiSlicePart<T> ep{static_cast<T*>(P.part), int64_t(P.rows)};
-      hipLaunchKernelGGL((k_tiled_pass<T, LL, Src, EpiSlicePart<T>>), dim3(P.grid), dim3(kNT), 0, s, P.rows,
-                         P.groups, P.ptr, P.idx, static_cast<const T*>(P.val), P.tiles, P.tbeg, first, ep,
-                         static_cast<double*>(nullptr));
-    }
-  });
-  LAUNCHCHK();
-  if (mid && P.S > 1) {
-    HIPCHK(hipEventRecord(mid->em, s));
-    mid->mid = true;
-  }
-  if (P.S > 1) {
-    CHK(run_combine<T>(P, P.S, rest, epi, partials, Pout, s));
-  } else if (Pout) {
-    *Pout = P.grid;
-  }
-  return KRCN_OK;
-  }
-  }
-}
-
-// The number of partials run_pass writes for plan P when its epilogue
-// reduces (the *Pout of a non-fused launch): the combine's grid for sliced
-// plans, the main launch's otherwise.  Row shards agree on its maximum over
-// ranks before the collectives (krcn_handle.hip agree_rows).
-inline int pass_partials(const PassPlan& P) {
-  auto combine = [&](int S) {
-    if (S <= kCombineSmallS) return combine_small_grid(P.rows);
-    if (combine_w_env() && S >= 32 && P.rows % 2 == 0 && combine_w_grid(P.rows, 2) <= P.pcap)
-      return combine_w_grid(P.rows, 2);   // (fp64 rows: CombW<double>::VW = 2; row shards are fp64)
-    return P.combine_grid;
-  };
-  if (P.jag) return (P.S > 1 && P.jG > 1) ? combine(P.jG) : P.grid;
-  if (P.win) return P.accum ? P.grid : combine(P.S);
-  return P.S > 1 ? combine(P.S) : P.grid;   // wave, sorted and dense plans
-}
-
-#if KRCN_FOLD
-// The early-alpha pass 1 of a window-slices plan with its slice combine
-// folded in (krcn_window.hpp EpiSliceFold; tuning builds).
-inline bool fold_ok(const krcn_csr* h) {
-  const PassPlan& P = h->p1;
-  return h->fcnt && P.win && !P.accum && P.R == 32 && P.S <= 96 && P.ntiles <= h->pcap;
-}
-template <typename T>
-inline krcn_status run_fold_pass1(krcn_csr* h, const SrcLzBeta<T>& src, const EpiSliceFold<T>& epi, hipStream_t s) {
-  PassPlan& P = h->p1;
-  WinArgs wa{P.rows, P.W, P.stride, P.S, 0, P.ntiles, P.cols, P.tb, P.ro, P.widx, P.val, P.segs};
-  wa.kpb = P.kpb;
-  hipLaunchKernelGGL((k_window_pass<T, 32, SrcLzBeta<T>, EpiSliceFold<T>, false>), dim3(P.grid), dim3(kWinNT), 0, s,
-                     wa, src, epi, static_cast<double*>(nullptr));
-  LAUNCHCHK();
-  return KRCN_OK;
-}
-#endif
-
-// Pass over X (rows) / X^T with a plain gathered vector.
-template <typename T, class Epi>
-inline krcn_status launch_rows_x(krcn_csr* h, const T* x, const Epi& epi, double* partials, int* P,
-                                 hipStream_t s) {
-  CHK(plans_for_compute(h));
-  return run_pass<T>(h->p1, SrcPlain<T>{x}, SrcPlain<T>{x}, epi, partials, P, s);
-}
-
-template <typename T, class Epi>
-inline krcn_status launch_rows_xt(krcn_csr* h, const T* u, const Epi& epi, double* partials, int* P,
-                                  hipStream_t s) {
-  CHK(plans_for_compute(h));
-  return run_pass<T>(h->p2, SrcPlain<T>{u}, SrcPlain<T>{u}, epi, partials, P, s);
-}
-
 // Lanczos recurrences, one translation unit per dtype (krcn_lanczos_impl.hpp).
 krcn_status lanczos_f64(krcn_csr* h, const double* w, const double* g, int m, int reorth, double tol, double l2,
                         double* V, double* alphas_host, double* betas_host, krcn_lanczos_info* info, hipStream_t s);
 krcn_status lanczos_f32(krcn_csr* h, const float* w, const float* g, int m, int reorth, double tol, double l2,
                         float* V, double* alphas_host, double* betas_host, krcn_lanczos_info* info, hipStream_t s);
 
-
+#include "krcn_pass.hpp"

@@ -51,10 +51,7 @@ template <typename T> struct CgsStepB {
 // round-3 kernels for A/B).
 template <typename T>
 static bool cgs_vec_ok(const krcn_csr* h, const T* V, const T* z, bool over_ranks, int k) {
-  static const bool env = [] {
-    const char* e = tuning_env("KRCN_CGS_1K");
-    return !(e && e[0] == '0');
-  }();
+  static const bool env = tuning_on("KRCN_CGS_1K");
   constexpr int E = Vec16<T>::E;
   const int64_t d = h->d;
   const int64_t ncg = (d / E + 63) / 64;
@@ -226,10 +223,7 @@ static uint64_t bits(double x) {
 // A/B knob KRCN_PACK_NORM=0: column shards keep the separate ||z||^2 all-reduce
 // (and so the two-collective step)
 static bool pack_env_ok() {
-  static const bool v = [] {
-    const char* e = tuning_env("KRCN_PACK_NORM");
-    return !(e && e[0] == '0');
-  }();
+  static const bool v = tuning_on("KRCN_PACK_NORM");
   return v;
 }
 
@@ -246,25 +240,17 @@ static krcn_status lanczos_impl(krcn_csr* h, const T* w, const T* g, int m, int 
   const bool cols = h->shard == KRCN_SHARD_COLS;
   // Step B fused into the next pass 1: LDS-window slices plans, unsharded, no
   // reorthogonalisation.
-  static const bool fuse_env = [] {
-    const char* e = tuning_env("KRCN_LANCZOS_FUSE");   // A/B knob: 0 keeps the separate step B
-    return !(e && e[0] == '0');
-  }();
-  const bool fuse_win = h->p1.win && !h->p1.accum && h->p1.grid % h->p1.S == 0;
-  const bool fuse_sorted = !h->p1.win && !h->p1.jag && h->p1.sorted && h->p1.S > 1;
-  const bool fuse_small = h->p1.win && h->p1.accum && h->p1.S == 1 && d <= kWinNT;
-  static const bool zw_env = [] {
-    const char* e = tuning_env("KRCN_ZW");   // A/B knob: 0 keeps pass 1's store of z_j
-    return !(e && e[0] == '0');
-  }();
+  static const bool fuse_env = tuning_on("KRCN_LANCZOS_FUSE");   // A/B knob: 0 keeps the separate step B
+  const int k1 = h->p1.kind, k2 = h->p2.kind;
+  const bool fuse_win = k1 == KRCN_PLAN_WINDOW_SLICES && h->p1.grid % h->p1.S == 0;
+  const bool fuse_sorted = k1 == KRCN_PLAN_SORTED && h->p1.S > 1;
+  const bool fuse_small = k1 == KRCN_PLAN_WINDOW_ACCUM && h->p1.S == 1 && d <= kWinNT;
+  static const bool zw_env = tuning_on("KRCN_ZW");   // A/B knob: 0 keeps pass 1's store of z_j
   const bool fuse = fuse_env && h->shard == KRCN_SHARD_NONE && !reorth && (fuse_win || fuse_sorted || fuse_small) &&
                     h->p1.grid <= h->pcap;
   // one-piece plans with per-block X^T copies: pass 2 folds into pass 1 plus
   // the partials' combine (A/B knob KRCN_XT_SMALL=0 keeps the X^T pass)
-  static const bool xt_env = [] {
-    const char* e = tuning_env("KRCN_XT_SMALL");
-    return !(e && e[0] == '0');
-  }();
+  static const bool xt_env = tuning_on("KRCN_XT_SMALL");
   const bool xt_small = fuse && fuse_small && h->p1.xt && xt_env && h->p1.grid <= h->pcap;
   // Two launches per step for plans whose pass 1 is unsliced sorted tiles and
   // pass 2 a single-window jagged pass: pass 1 with step B fused stores
@@ -272,13 +258,12 @@ static krcn_status lanczos_impl(krcn_csr* h, const T* w, const T* g, int m, int 
   // gathers u = u' / beta (SrcLzU), where the plain path would run a
   // separate step B.  No BASELINE config gets such a plan by default (the
   // plan policy that would give rcv1 one lost, krcn_plan.hip ensure_plans);
-  // krcn_csr_set_pass_format reaches it.  (A/B knob KRCN_LZ2=0: off.)
-  static const bool lz2_env = [] {
-    const char* e = tuning_env("KRCN_LZ2");
-    return !(e && e[0] == '0');
-  }();
-  const bool fuse_u = fuse_env && lz2_env && h->shard == KRCN_SHARD_NONE && !reorth && h->p1.sorted && !h->p1.win &&
-                      !h->p1.jag && h->p1.S == 1 && h->p2.jag && h->p2.S == 1 && h->p1.grid <= h->pcap;
+  // krcn_csr_set_pass_format reaches it.  (A/B knob KRCN_LZ2=0: off.  The
+  // plan policy reads the same knob as off unless 1, krcn_plan.hip
+  // ensure_plans: whether the auto policy builds such a pair of plans.)
+  static const bool lz2_env = tuning_on("KRCN_LZ2");
+  const bool fuse_u = fuse_env && lz2_env && h->shard == KRCN_SHARD_NONE && !reorth && k1 == KRCN_PLAN_SORTED &&
+                      h->p1.S == 1 && k2 == KRCN_PLAN_JAG && h->p2.S == 1 && h->p1.grid <= h->pcap;
   // Early alpha (window-slices or sliced sorted-tile pass 1; krcn_kernels.hpp
   // EpiLz2E): the slice combine also forms the partials of (X v_j).(w X v_j),
   // pass 2 settles alpha_j from them in its prologue and runs step B in its
@@ -287,11 +272,8 @@ static krcn_status lanczos_impl(krcn_csr* h, const T* w, const T* g, int m, int 
   // per block (Red2): the single-window and one-group accumulate jagged
   // passes and the accumulate window pass do.  (A/B knob KRCN_LZ_EARLY=0:
   // the fused window step of rounds 2-4.)
-  static const bool early_env = [] {
-    const char* e = tuning_env("KRCN_LZ_EARLY");
-    return !(e && e[0] == '0');
-  }();
-  const bool p2_red2 = (h->p2.jag && (h->p2.S == 1 || h->p2.jG == 1)) || (h->p2.win && h->p2.accum);
+  static const bool early_env = tuning_on("KRCN_LZ_EARLY");
+  const bool p2_red2 = (k2 == KRCN_PLAN_JAG && (h->p2.S == 1 || h->p2.jG == 1)) || k2 == KRCN_PLAN_WINDOW_ACCUM;
   // window-slices (news20) and sliced sorted-tile (rcv1) pass-1 plans: the
   // early step replaces their fused step B (pass 1 then gathers one vector
   // instead of forming z = w - alpha v from two)
@@ -364,10 +346,7 @@ static krcn_status lanczos_impl(krcn_csr* h, const T* w, const T* g, int m, int 
   // apply after the all-reduce runs it (SrcLzStep: beta, the breakdown test,
   // the state) from u[n].  The last loop step keeps the scalar all-reduce:
   // k_lz_final_check reads that norm.
-  static const bool pack_env = [] {
-    const char* e = tuning_env("KRCN_PACK_NORM");   // A/B knob: 0 keeps the separate all-reduce
-    return !(e && e[0] == '0');
-  }();
+  static const bool pack_env = tuning_on("KRCN_PACK_NORM");   // A/B knob: 0 keeps the separate all-reduce
   const bool pack = cols && std::is_same<T, double>::value && !reorth && pack_env;
   bool packed = false;   // u[n] holds this rank's ||z_j||^2 for the coming step
   double* const unorm = static_cast<double*>(h->u) + n;
@@ -593,13 +572,9 @@ static krcn_status lanczos_impl(krcn_csr* h, const T* w, const T* g, int m, int 
       if (xt_small) {
         // pass 2 = the blocks' X^T u partials added in k_slice_combine's fixed
         // order, with step A in its epilogue
-        static const bool xt_comb_env = [] {   // A/B knob: 0 uses k_slice_combine
-          const char* e = tuning_env("KRCN_XT_COMB");
-          return !(e && e[0] == '0');
-        }();
+        static const bool xt_comb_env = tuning_on("KRCN_XT_COMB");   // A/B knob: 0 uses k_slice_combine
         static const int xt_rb = [] {   // A/B knob: rows per combine block (16 / 32 / 64)
-          const char* e = tuning_env("KRCN_XT_RB");
-          const int v = e ? atoi(e) : kXtCombineRows;
+          const int v = tuning_value("KRCN_XT_RB", kXtCombineRows);
           return v == 16 || v == 64 ? v : 32;
         }();
         if (xt_comb_env) {
@@ -637,10 +612,7 @@ static krcn_status lanczos_impl(krcn_csr* h, const T* w, const T* g, int m, int 
     // round 4: a reorthogonalised step on the 1 KiB-piece CGS2 path forms
     // step B inside its first sweep (k_cgs_rowdots_vb): no k_lz_step_b launch
     // (tuning knob KRCN_CGS_FUSEB=0 keeps the launch)
-    static const bool fuseb_env = [] {
-      const char* e = tuning_env("KRCN_CGS_FUSEB");
-      return !(e && e[0] == '0');
-    }();
+    static const bool fuseb_env = tuning_on("KRCN_CGS_FUSEB");
     const bool fuse_b = reorth && fuseb_env && cgs_vec_ok<T>(h, V, zn, dshard, j + 1);
     if (!fuse_b) {
       hipLaunchKernelGGL((k_lz_step_b<T>), dim3(Pb), dim3(kNT), 0, s, d, static_cast<const T*>(W), c, pa_g, Pa,

@@ -110,7 +110,7 @@ static krcn_status build_slices(PassPlan& P, const int* ptr, const int* idx, con
 // long row) as nonzero offsets.
 static krcn_status build_tiles(PassPlan& P, hipStream_t s, std::vector<int>* segs, std::vector<int>* segbase) {
   const int S = P.S, rows = P.rows;
-  const bool sorted = P.sorted != 0;
+  const bool sorted = P.kind == KRCN_PLAN_SORTED;
   const int sort_tile = P.sort_nt * kSortPerThread;
   const int cap_nnz = sorted ? sort_tile : kWaveTileNnz;
   const int cap_rows = sorted ? sort_tile / 4 : kWaveTileRows;
@@ -279,9 +279,8 @@ static constexpr int64_t kSortWindowDefault = 24576;
 
 static int64_t sort_window() {
   static const int64_t w = [] {
-    const char* e = tuning_env("KRCN_SORT_WINDOW");   // tuning knob
-    const long long v = e ? atoll(e) : 0;
-    return v >= 1024 ? int64_t(v) : kSortWindowDefault;
+    const int64_t v = tuning_value("KRCN_SORT_WINDOW", int64_t(0));   // tuning knob
+    return v >= 1024 ? v : kSortWindowDefault;
   }();
   return w;
 }
@@ -312,10 +311,8 @@ static int64_t win_width() { return WinGeom<T>::kW; }
 
 static int win_slices_mode(int64_t cols, int64_t Wmax, int* k_out) {
   const int64_t smin = (cols + Wmax - 1) / Wmax;
-  static const int k_env = [] {   // A/B knob: blocks per slice (S = 256 / k slices, e.g. k = 3: 85)
-    const char* e = tuning_env("KRCN_WIN_KPB");
-    return e ? atoi(e) : 0;
-  }();
+  // A/B knob: blocks per slice (S = 256 / k slices, e.g. k = 3: 85)
+  static const int k_env = tuning_value("KRCN_WIN_KPB", 0);
   if (k_env >= 2 && k_env <= 8 && kNumCUs / k_env >= smin) {
     *k_out = k_env;
     return kNumCUs / k_env;
@@ -330,10 +327,7 @@ static int win_slices_mode(int64_t cols, int64_t Wmax, int* k_out) {
     *k_out = 3;
     return kNumCUs / 3;
   }
-  static const int s_env = [] {   // A/B knob: minimum slice count (a power of two)
-    const char* e = tuning_env("KRCN_WIN_MIN_SLICES");
-    return e ? atoi(e) : 0;
-  }();
+  static const int s_env = tuning_value("KRCN_WIN_MIN_SLICES", 0);   // A/B knob: minimum slice count (a power of two)
   for (int S = 8; S <= kNumCUs; S *= 2)
     if (S >= smin && S >= s_env) { *k_out = kNumCUs / S; return S; }
   for (int S = 8; S <= kNumCUs; S *= 2)
@@ -346,10 +340,7 @@ static int win_slices_mode(int64_t cols, int64_t Wmax, int* k_out) {
 // arrays into physically contiguous allocations (hipDeviceMallocContiguous),
 // 2 into fresh plain allocations made after the build's temporaries are gone.
 static int plan_reloc_env() {
-  static const int v = [] {
-    const char* e = tuning_env("KRCN_PLAN_RELOC");
-    return e ? atoi(e) : 0;
-  }();
+  static const int v = tuning_value("KRCN_PLAN_RELOC", 0);
   return v;
 }
 
@@ -371,10 +362,7 @@ static krcn_status plan_reloc(PassPlan& P, void* field, hipStream_t s) {
 
 // 0: no window format, 1: accumulate, 2: slices (auto policy).
 static double slice_min_mat() {   // matrix bytes below which slices + combine do not pay
-  static const double v = [] {
-    const char* e = tuning_env("KRCN_SLICE_MIN_MB");   // A/B knob
-    return e ? atof(e) * 1e6 : 48e6;
-  }();
+  static const double v = tuning_value("KRCN_SLICE_MIN_MB", 48.0) * 1e6;   // A/B knob
   return v;
 }
 static int window_choice(int rows, int64_t cols, int64_t nnz, size_t vs) {
@@ -480,8 +468,7 @@ static krcn_status build_window(PassPlan& P, const int* ptr, const int* idx, con
   const int W = int((cols + S - 1) / S);
   P.S = S;
   P.W = W;
-  P.win = 1;
-  P.accum = accum;
+  P.kind = accum ? KRCN_PLAN_WINDOW_ACCUM : KRCN_PLAN_WINDOW_SLICES;
   P.L = 1;
   P.groups = 1;
   std::vector<int> hb(S + 1);
@@ -507,8 +494,8 @@ static krcn_status build_window(PassPlan& P, const int* ptr, const int* idx, con
   // (profiles/r03_news20_winR.txt); the few tiles past 256 take one extra chunk.
   const double mean = double(nnz) / (double(rows) * double(S));
   P.R = mean * 64.0 <= 0.95 * kWinChunk ? 64 : mean * 32.0 <= 0.95 * kWinChunk ? 32 : 16;
-  if (const char* e = tuning_env("KRCN_WIN_R")) {   // A/B knob: rows per tile (16 / 32 / 64)
-    const int r = atoi(e);
+  {
+    const int r = tuning_value("KRCN_WIN_R", 0);   // A/B knob: rows per tile (16 / 32 / 64)
     if (r == 16 || r == 32 || r == 64) P.R = r;
   }
   const int R = P.R;
@@ -551,8 +538,7 @@ static krcn_status build_window(PassPlan& P, const int* ptr, const int* idx, con
       return c;
     };
     const int cap = kWinWaves * kWinTMax;   // tiles per block (register sums)
-    int B = kNumCUs;
-    if (const char* e = tuning_env("KRCN_WIN_ACC_B")) B = std::max(1, atoi(e));   // A/B knob: first grid tried
+    int B = std::max(1, tuning_value("KRCN_WIN_ACC_B", kNumCUs));   // A/B knob: first grid tried
     std::vector<int> cut;
     for (;;) {
       cut = cut_ranges(B, cost);
@@ -608,10 +594,7 @@ static constexpr int kJagGroupCost = 96;   // fixed work per group and slice, in
 // KRCN_JAG (A/B knob): 0 never by the auto policy, 1 the cost model (default),
 // 2 every pass the format can run
 static int jag_env() {
-  static const int v = [] {
-    const char* e = tuning_env("KRCN_JAG");
-    return e ? atoi(e) : 1;
-  }();
+  static const int v = tuning_value("KRCN_JAG", 1);
   return v;
 }
 
@@ -695,10 +678,7 @@ static bool jag_choice(int rows, int64_t cols, int64_t nnz, int pass) {
   const double mean = double(nnz) / double(rows) / double(S);   // elements per row and slice
   if (S == 1) {
     // A/B knob: KRCN_JAG_S1G=g sets the row groups a single-window plan needs
-    static const int64_t genv = [] {
-      const char* e = tuning_env("KRCN_JAG_S1G");
-      return e ? int64_t(atoi(e)) : int64_t(0);
-    }();
+    static const int64_t genv = tuning_value("KRCN_JAG_S1G", 0);
     const bool relaxed = pass == 2 && sizeof(T) == 8;   // (fp32 rcv1 stress: 10.4 -> 14.7 us, kept off)
     const int64_t gmin = genv > 0 ? genv : relaxed ? int64_t(kJagS1MinGroupsXt) : int64_t(kNumCUs) * kJagWaves;
     return G >= gmin && mean <= 48.0;
@@ -727,10 +707,8 @@ static krcn_status build_jag(PassPlan& P, const int* ptr, const int* idx, const 
   // A/B knob: force the slice-group count of accumulate plans, KRCN_JAG_G=g
   // (both passes) or g1,g2 (pass 1 / pass 2; 0 keeps the cost model's)
   static const std::pair<int, int> g_env = [] {
-    const char* e = tuning_env("KRCN_JAG_G");
-    int a = 0, b = 0;
-    if (e && std::sscanf(e, "%d,%d", &a, &b) == 1) b = a;
-    return std::make_pair(a, b);
+    const int a = tuning_value("KRCN_JAG_G", 0);
+    return std::make_pair(a, tuning_value("KRCN_JAG_G", a, 1));
   }();
   const int gf = pass == 1 ? g_env.first : g_env.second;
   // slice groups (their partials change the summation order: never under the
@@ -770,10 +748,7 @@ static krcn_status build_jag(PassPlan& P, const int* ptr, const int* idx, const 
   }
   {
     // A/B knob KRCN_JAG_LONG=t: rows past t elements go long (8..254)
-    static const int long_env = [] {
-      const char* e = tuning_env("KRCN_JAG_LONG");
-      return e ? atoi(e) : 0;
-    }();
+    static const int long_env = tuning_value("KRCN_JAG_LONG", 0);
     if (lthr > 0 && long_env >= 8 && long_env <= 254) lthr = long_env;
   }
   if (lthr > 0)
@@ -796,10 +771,7 @@ static krcn_status build_jag(PassPlan& P, const int* ptr, const int* idx, const 
   if (S == 1) {
     // fewer groups than waves: blocks of >= kJagS1GroupsPerBlock groups, so
     // fewer blocks load the whole window (A/B knob: KRCN_JAG_R=r caps them)
-    static const int rcap = [] {
-      const char* e = tuning_env("KRCN_JAG_R");
-      return e ? atoi(e) : 0;
-    }();
+    static const int rcap = tuning_value("KRCN_JAG_R", 0);
     if (G < kNumCUs * kJagWaves) R = std::max(1, std::min(R, G / kJagS1GroupsPerBlock));
     if (rcap > 0) R = std::min(R, rcap);
   }
@@ -987,7 +959,7 @@ static krcn_status build_jag(PassPlan& P, const int* ptr, const int* idx, const 
                        cnt8.p, reinterpret_cast<unsigned long long*>(P.jcnt));
   LAUNCHCHK();
   HIPCHK(hipStreamSynchronize(s));
-  P.jag = 1;
+  P.kind = KRCN_PLAN_JAG;
   P.jlong = nl;
   P.jlpiece = lpiece;
   P.jK = K;
@@ -1022,7 +994,7 @@ static krcn_status build_dense_as(PassPlan& P, const int* ptr, const int* idx, c
   }
   if (g.S > 1) CHK(P.own.alloc(&P.part, sizeof(T) * size_t(g.S) * size_t(std::max(P.rows, 1))));
   HIPCHK(hipStreamSynchronize(s));
-  P.dense = 1;
+  P.kind = KRCN_PLAN_DENSE;
   P.dld = g.ld;
   P.dvs = int(sizeof(TS));
   P.S = g.S;
@@ -1081,8 +1053,8 @@ static krcn_status dense_value_bytes(const krcn_csr* h, hipStream_t s, size_t* v
 // values; unset keeps the handle's).
 static int pass_format(const krcn_csr* h, int pass) {
   int fmt = h->format_pass[pass - 1] >= 0 ? h->format_pass[pass - 1] : h->format;
-  static const int f1 = [] { const char* e = tuning_env("KRCN_FMT1"); return e ? atoi(e) : -1; }();
-  static const int f2 = [] { const char* e = tuning_env("KRCN_FMT2"); return e ? atoi(e) : -1; }();
+  static const int f1 = tuning_value("KRCN_FMT1", -1);
+  static const int f2 = tuning_value("KRCN_FMT2", -1);
   const int f = pass == 2 ? f2 : f1;
   if (f >= KRCN_FORMAT_AUTO && f <= KRCN_FORMAT_DENSE) fmt = f;
   return fmt;
@@ -1189,7 +1161,7 @@ static krcn_status build_plan(krcn_csr* h, int pass, int rows, int64_t cols, int
     P.S = slices_for(cols * int64_t(sizeof(T)));
   }
   if (P.S > 1 && cols < P.S) P.S = 1;
-  P.sorted = sorted ? 1 : 0;
+  P.kind = sorted ? KRCN_PLAN_SORTED : KRCN_PLAN_WAVE;
   P.sort_nt = sort_nt;
   P.groups = P.S > 1 ? 8 : 1;
   // a sliced row holds ~1/S of its nonzeros: pick lanes from the slice-local mean
@@ -1226,8 +1198,8 @@ static krcn_status build_plan(krcn_csr* h, int pass, int rows, int64_t cols, int
     CHK(P.own.alloc(&P.part, sizeof(T) * size_t(P.S) * std::max(rows, 1)));
   }
   std::vector<int> segs, segbase;
-  CHK(build_tiles(P, s, P.sorted ? &segs : nullptr, P.sorted ? &segbase : nullptr));
-  if (P.sorted) CHK(build_sorted<T>(P, segs, segbase, s));
+  CHK(build_tiles(P, s, sorted ? &segs : nullptr, sorted ? &segbase : nullptr));
+  if (sorted) CHK(build_sorted<T>(P, segs, segbase, s));
   return KRCN_OK;
 }
 
@@ -1255,7 +1227,7 @@ static krcn_status build_plans(krcn_csr* h, bool lz2, hipStream_t s) {
     }
   }
   CHK(build_plan<T>(h, 2, int(h->d), h->n, h->nnz, h->tptr, h->tidx, static_cast<const T*>(h->tval), h->lanes_xt, s));
-  h->p1_unsliced = lz2 && h->p2.jag && h->p2.S == 1 && h->shard == KRCN_SHARD_NONE;
+  h->p1_unsliced = lz2 && h->p2.kind == KRCN_PLAN_JAG && h->p2.S == 1 && h->shard == KRCN_SHARD_NONE;
   return build_plan<T>(h, 1, int(h->n), h->d, h->nnz, h->ptr, h->idx, static_cast<const T*>(h->val), h->lanes_x, s);
 }
 
@@ -1272,11 +1244,10 @@ krcn_status ensure_plans(krcn_csr* h) {
   // 1's slicing.  Off by default: unslicing rcv1's sorted pass 1 for the
   // two-launch step ran 33.4-34.1 k HVP/s against 43.3-44.2 k for the sliced
   // pass + combine (pass 1 16 against 10 us, pass 2 13.7 against 10.3 us;
-  // profiles/r04_rcv1_lz2.txt).  A/B knob KRCN_LZ2=1 turns it on.
-  static const bool lz2_env = [] {
-    const char* e = tuning_env("KRCN_LZ2");
-    return e && e[0] == '1';
-  }();
+  // profiles/r04_rcv1_lz2.txt).  A/B knob KRCN_LZ2=1 turns it on.  (The
+  // step itself reads the same knob as on unless 0, krcn_lanczos_impl.hpp
+  // lanczos_impl fuse_u: it runs wherever a plan allows it.)
+  static const bool lz2_env = tuning_off("KRCN_LZ2");
   krcn_status r = h->dtype == KRCN_F64 ? build_plans<double>(h, lz2_env, s) : build_plans<float>(h, lz2_env, s);
   (void)hipStreamDestroy(s);
   CHK(r);
@@ -1297,7 +1268,7 @@ krcn_status ensure_plans(krcn_csr* h) {
   h->p1.pcap = h->p2.pcap = h->pcap;
 #if KRCN_FOLD
   CHK(h->own.release(&h->fcnt));
-  if (h->p1.win && !h->p1.accum && h->p1.ntiles > 0) {   // tickets (ntiles), then the per-block won lists
+  if (h->p1.kind == KRCN_PLAN_WINDOW_SLICES && h->p1.ntiles > 0) {   // tickets (ntiles), then the per-block won lists
     const size_t cnt = size_t(h->p1.ntiles) * size_t(kFoldPad + h->p1.grid);
     CHK(h->own.alloc(&h->fcnt, sizeof(int) * cnt));
     HIPCHK(hipMemset(h->fcnt, 0, sizeof(int) * cnt));
