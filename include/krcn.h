@@ -125,12 +125,37 @@ enum { KRCN_FORMAT_AUTO = 0, KRCN_FORMAT_WAVE = 1, KRCN_FORMAT_SORTED = 2, KRCN_
 
 /* Stored width of the matrix values in the pass plans.  Arithmetic, vectors
  * and sums keep the handle's dtype.
- * Only dense passes (KRCN_FORMAT_DENSE) honour the policy: a pass on a CSR
- * format keeps full width and reports sizeof(dtype) from
- * krcn_csr_plan_value_bytes.  On a KRCN_F32 handle every policy is a no-op
+ * Scope: on a KRCN_F64 handle KRCN_VALUES_F32 and _F32_EXACT narrow dense,
+ * window-slices, window-accum and jagged passes (KRCN_PLAN_DENSE,
+ * _WINDOW_SLICES, _WINDOW_ACCUM, _JAG).  Wave and sorted passes keep full
+ * width.  krcn_csr_plan_value_bytes reports 4 for a narrowed pass and
+ * sizeof(dtype) otherwise.  On a KRCN_F32 handle every policy is a no-op
  * (both passes report 4, results are bitwise the same).  The policy touches
  * the pass plans only: krcn_csr_get_transpose and the coordinate calls
  * (krcn_coord_*) read the handle's transposed CSR, which stays full width.
+ * No default picks a narrowed plan.
+ * A narrowed window or jagged pass on a KRCN_F64 handle:
+ *   - Values: each stored value is static_cast<float>(v), the long-row arrays
+ *     of a jagged plan included; it is widened to double when loaded (exact),
+ *     and products, the LDS slabs, sums, partials and epilogues stay fp64.
+ *     Pads stay zero.
+ *   - Summation order: the full-width order of that format.  A narrowed pass
+ *     is bitwise the full-width pass of the same plan over A32 =
+ *     double(float(A)); wherever the full-width pass is bitwise scipy, the
+ *     narrowed pass is bitwise scipy on A32.
+ *   - Geometry and choice do not depend on the stored width: the automatic
+ *     format choice, slices, tiles, lanes, grids and the jagged long-row rule
+ *     are those of the full-width plan; krcn_csr_plan_info and
+ *     krcn_csr_plan_format equal the full-width handle's.  Only the element
+ *     type of the value arrays changes (10 -> 6 bytes per nonzero).
+ *   - One matrix per operator: a window or jagged pass narrows only if the
+ *     other pass narrows too (it is dense, window or jagged).  Otherwise both
+ *     stay full width: an automatic plan with a sorted pass 1 and a jagged
+ *     pass 2 never computes A32^T diag(w) A.  (A dense pass narrows whatever
+ *     its partner is: dense + wave computes with A32 in the dense pass only.)
+ *   - Internal copies: every copy of the matrix a narrowed plan holds carries
+ *     A32.  The per-block X^T copy of a one-piece window-accum plan stores the
+ *     widened rounded values at 8 bytes.
  * A narrowed dense pass on a KRCN_F64 handle:
  *   - Values: the image stores static_cast<float>(v) (round to nearest even);
  *     the kernel widens each stored value to double, which is exact, and

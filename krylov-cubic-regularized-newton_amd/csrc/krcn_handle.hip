@@ -326,7 +326,7 @@ extern "C" krcn_status krcn_csr_plan_value_bytes(krcn_csr* h, int* out2_host) {
   CHK(set_device(h));
   CHK(ensure_plans(h));
   const PassPlan* ps[2] = {&h->p1, &h->p2};
-  for (int i = 0; i < 2; ++i) out2_host[i] = ps[i]->kind == KRCN_PLAN_DENSE ? ps[i]->dvs : int(h->vs);
+  for (int i = 0; i < 2; ++i) out2_host[i] = ps[i]->vbytes;
   return KRCN_OK;
 }
 

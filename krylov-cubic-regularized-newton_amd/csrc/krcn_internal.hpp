@@ -251,6 +251,8 @@ struct PlanFields {
   int* tbeg = nullptr;        // groups + 1 tile offsets
   void* part = nullptr;       // S * rows partial row sums (sliced)
   int kind = KRCN_PLAN_WAVE;  // the format (KRCN_PLAN_*): the one kernel family that runs the plan
+  int vbytes = 0;             // bytes per stored matrix value: the handle's value size, or 4 in a dense, window or
+                              // jagged plan of an fp64 handle under KRCN_VALUES_F32 (val, own_val, jlval)
   // sorted block tiles (k_sorted_pass) instead of wave tiles
   int sort_nt = 256;          // sorted tiles: threads per block (tile = kSortPerThread x sort_nt nonzeros)
   unsigned* gword = nullptr;  // sorted tiles: (column - tile base) << kSortSlotBits | CSR slot
@@ -286,7 +288,6 @@ struct PlanFields {
   void* xpart = nullptr;      //   per block X^T u partials (grid x cols)
   // dense format (k_dense_pass; S, L, grid, ntiles = row groups, own_val = the image)
   int64_t dld = 0;            //   entries per image row
-  int dvs = 0;                //   bytes per stored image value (sizeof(T), or 4 under KRCN_VALUES_F32)
   int64_t pcap = 0;           // entries of the handle's partials buffers (ensure_plans)
 };
 // ... and the owner of every device buffer those fields point to.
@@ -310,8 +311,8 @@ struct krcn_csr {
   int slicing = KRCN_SLICING_AUTO;
   int format = KRCN_FORMAT_AUTO;
   int format_pass[2] = {-1, -1};   // krcn_csr_set_pass_format (-1: the handle's format)
-  int values = KRCN_VALUES_FULL;   // krcn_csr_set_value_storage: stored width of the dense images' values
-  size_t dense_vs = 8;             //   bytes per stored value the current plan build decided on (build_plans)
+  int values = KRCN_VALUES_FULL;   // krcn_csr_set_value_storage: stored width of the narrowing plans' values
+  size_t store_vs = 8;             //   bytes per stored value the current plan build decided on (build_plans)
   int sort_nt = 0;            // sorted-tile block size; 0 = by matrix size
   bool plans_ready = false;
   bool p1_unsliced = false;   // pass 2 took a single-window jagged plan: pass 1's sorted tiles go

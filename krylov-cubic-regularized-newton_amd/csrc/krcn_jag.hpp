@@ -35,7 +35,10 @@
 //  * accumulate: a unit's elements are row-major (lane 0's, lane 1's, ...),
 //    padded to an even count (see k_jag_acc);
 //  * elements: 16-bit slice-local column offsets + values (10 B / nonzero,
-//    plus the pads).
+//    plus the pads; 6 B when an fp64 handle stores fp32 values,
+//    KRCN_VALUES_F32: the kernels' stored type TS — a lane's value pair is
+//    then one 8-byte load, widened at the multiply; order, pads, counts and
+//    unit metadata are the full-width plan's).
 //
 // Pipeline: a wave's work is a fixed sequence of chunks (unit i, levels
 // ch LC .. + LC) — K x CPG per slice, unrolled — and the loads of chunk q + 1
@@ -201,21 +204,23 @@ typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 
 // One chunk of LC levels (LC / 2 pair levels) of a unit in flight (a lane's
 // level k is live when its count exceeds k: recomputed at consumption).
-template <typename T, int LC> struct JagChunk {
+// TS is the stored type of the values (T, or float under fp64 arithmetic:
+// KRCN_VALUES_F32): a pair is then one 8-byte load, widened at the multiply.
+template <typename T, typename TS, int LC> struct JagChunk {
   static_assert(LC % 2 == 0, "whole pair levels");
   u16x2 o[LC / 2];
-  typename JagPair<T>::type v[LC / 2];
+  typename JagPair<TS>::type v[LC / 2];
 };
 
 // Positions of pair levels [k0 / 2, (k0 + LC) / 2) for this lane (count c)
 // and their loads; `cum` (wave-uniform) advances past the chunk's slots.
 // Inactive lanes load from `cum` (an address shared by the wave, in bounds:
 // the arrays are padded).
-template <typename T, int LC>
-__device__ __forceinline__ void jag_issue(JagChunk<T, LC>& C, int c, int k0, int& cum, const JagArgs& a) {
-  typedef typename JagPair<T>::type T2;
+template <typename T, typename TS, int LC>
+__device__ __forceinline__ void jag_issue(JagChunk<T, TS, LC>& C, int c, int k0, int& cum, const JagArgs& a) {
+  typedef typename JagPair<TS>::type T2;
   const unsigned short* __restrict__ widx = a.widx;
-  const T* __restrict__ wval = static_cast<const T*>(a.wval);
+  const TS* __restrict__ wval = static_cast<const TS*>(a.wval);
 #pragma unroll
   for (int j = 0; j < LC / 2; ++j) {
     const bool act = c > k0 + 2 * j;
@@ -229,13 +234,13 @@ __device__ __forceinline__ void jag_issue(JagChunk<T, LC>& C, int c, int k0, int
 }
 
 // Levels k0 .. k0 + LC - 1 added left to right (the CSR order of the row).
-template <typename T, int LC>
-__device__ __forceinline__ T jag_consume(const JagChunk<T, LC>& C, int c, int k0, const T* win, T acc) {
+template <typename T, typename TS, int LC>
+__device__ __forceinline__ T jag_consume(const JagChunk<T, TS, LC>& C, int c, int k0, const T* win, T acc) {
 #pragma unroll
   for (int j = 0; j < LC / 2; ++j) {
-    const T p0 = C.v[j].x * win[C.o[j].x];
+    const T p0 = T(C.v[j].x) * win[C.o[j].x];
     acc = c > k0 + 2 * j ? acc + p0 : acc;
-    const T p1 = C.v[j].y * win[C.o[j].y];
+    const T p1 = T(C.v[j].y) * win[C.o[j].y];
     acc = c > k0 + 2 * j + 1 ? acc + p1 : acc;
   }
   return acc;
@@ -269,15 +274,15 @@ template <typename T> __device__ __forceinline__ T wave_sum_t(T v) {
 // with news20's X^T rows past 16 sent to tasks, KRCN_JAG_LONG=16, pass 2 ran 27.9-28.5 us against the
 // default's 27.4-27.8: profiles/r06ah_news20_long16_ab.txt)
 #endif
-template <typename T> struct JagLong {
-  typedef typename JagPair<T>::type T2;
+template <typename T, typename TS> struct JagLong {
+  typedef typename JagPair<TS>::type T2;
   int t0, t1, ntw, dp, dn;
   u16x2 oc;
   T2 vc;
   __device__ __forceinline__ void ld(const JagArgs& a, int j, u16x2& o, T2& v, int lane) const {
     const int p = __builtin_amdgcn_readlane(dp, j) + 2 * lane;
     o = *reinterpret_cast<const u16x2*>(a.lidx + p);
-    v = *reinterpret_cast<const T2*>(static_cast<const T*>(a.lval) + p);
+    v = *reinterpret_cast<const T2*>(static_cast<const TS*>(a.lval) + p);
   }
   // this wave's task list (lane j < 16: task j's start and count)
   __device__ __forceinline__ void desc(const JagArgs& a, int b, int wave, int lane) {
@@ -292,10 +297,10 @@ template <typename T> struct JagLong {
   // the first task's loads
   __device__ __forceinline__ void first(const JagArgs& a, int lane) { ld(a, 0, oc, vc, lane); }
 };
-template <typename T, class Epi>
+template <typename T, typename TS, class Epi>
 __device__ __forceinline__ typename RedOf<Epi>::type jag_long_rows(const JagArgs& a, const Epi& epi, const T* win, T* lpart, int b,
-                                                int wave, int lane, JagLong<T>& L) {
-  typedef typename JagPair<T>::type T2;
+                                                int wave, int lane, JagLong<T, TS>& L) {
+  typedef typename JagPair<TS>::type T2;
   if (!KRCN_JAG_LONG_EARLY) {
     L.desc(a, b, wave, lane);
     L.first(a, lane);
@@ -308,8 +313,8 @@ __device__ __forceinline__ typename RedOf<Epi>::type jag_long_rows(const JagArgs
   for (int j = 0; j < L.ntw; ++j) {
     L.ld(a, j + 1 < 16 ? j + 1 : 15, on, vn, lane);   // unconditional (in bounds): the next task's loads in flight
     const int n = __builtin_amdgcn_readlane(L.dn, j);
-    const T p0 = 2 * lane < n ? vc.x * win[oc.x] : T(0);
-    const T p1 = 2 * lane + 1 < n ? vc.y * win[oc.y] : T(0);
+    const T p0 = 2 * lane < n ? T(vc.x) * win[oc.x] : T(0);
+    const T p1 = 2 * lane + 1 < n ? T(vc.y) * win[oc.y] : T(0);
     const T s = wave_sum_t<T>(p0 + p1);
     if (lane == 0) lpart[wave + kJagWaves * j] = s;
     oc = on;
@@ -386,8 +391,9 @@ __device__ __forceinline__ void jag_block_red(double v, double*, double* sm, dou
 }
 
 // The single-window jagged pass (S == 1): the vector in LDS whole, each unit
-// flushed to the epilogue as soon as it is summed.
-template <typename T, int K, int CPG, int CB, class Src, class Epi>
+// flushed to the epilogue as soon as it is summed.  TS: the stored type of
+// the plan's values (JagChunk); the window, sums and epilogue are T's.
+template <typename T, typename TS, int K, int CPG, int CB, class Src, class Epi>
 __global__ __launch_bounds__(kJagNT, 1) void k_jag_pass(JagArgs a, Src src, Epi epi, double* __restrict__ partials) {
   constexpr int LC = kJagLC;
   constexpr int Q = K * CPG;                 // chunks per wave
@@ -419,7 +425,7 @@ __global__ __launch_bounds__(kJagNT, 1) void k_jag_pass(JagArgs a, Src src, Epi 
   jag_fetch<T, R>(tmp, xe, 0, a.cols, NP);
   // long-row tasks: the descriptors behind the window burst, the first task's
   // loads before the units (KRCN_JAG_LONG_EARLY) or after them
-  JagLong<T> jl;
+  JagLong<T, TS> jl;
   if (KRCN_JAG_LONG_EARLY && a.nlong > 0) jl.desc(a, b, wave, lane);
   // a count byte of 0xFF marks a long row (summed below, not in the units):
   // its lane counts 0 in the units and skips the unit epilogue (formed after
@@ -435,13 +441,13 @@ __global__ __launch_bounds__(kJagNT, 1) void k_jag_pass(JagArgs a, Src src, Epi 
 #pragma unroll
     for (int i = 0; i < K; ++i) cum[i] = __builtin_amdgcn_readlane(bv, i);
   };
-  JagChunk<T, LC> C[2];
+  JagChunk<T, TS, LC> C[2];
 #if KRCN_JAG_EARLY
   // the first chunk does not depend on the source: it streams in behind the
   // window fetch (the counts were loaded before it, so waiting for them does
   // not drain the window burst)
   decode(bvec);
-  jag_issue<T, LC>(C[0], jag_count<CB>(cw, 0), 0, cum[0], a);
+  jag_issue<T, TS, LC>(C[0], jag_count<CB>(cw, 0), 0, cum[0], a);
 #endif
   bool split = false;
   if constexpr (IsSplitSrc<Src>::value) split = src.pre_ok;
@@ -473,7 +479,7 @@ __global__ __launch_bounds__(kJagNT, 1) void k_jag_pass(JagArgs a, Src src, Epi 
   typename RedOf<Epi>::type red{};
 #if !KRCN_JAG_EARLY
   decode(bvec);
-  jag_issue<T, LC>(C[0], jag_count<CB>(cw, 0), 0, cum[0], a);
+  jag_issue<T, TS, LC>(C[0], jag_count<CB>(cw, 0), 0, cum[0], a);
 #endif
   // levels past the static chunks.  Plans of K <= 2 units a wave (rcv1's
   // X^T: 33-60-element rows past the 16 static levels, 2-6 chunks a wave)
@@ -484,12 +490,12 @@ __global__ __launch_bounds__(kJagNT, 1) void k_jag_pass(JagArgs a, Src src, Epi 
   // two more chunks would spill.  Same levels, same order: the bits do not
   // change.
   constexpr bool kOvfPipe = K <= 2;
-  JagChunk<T, LC> X0, X1;
+  JagChunk<T, TS, LC> X0, X1;
   auto overflow_issue = [&](int i) {
     if constexpr (!kOvfPipe) return true;
     const int c = jag_count<CB>(cw, i);
     const bool any = __ballot(c > CPG * LC) != 0ull;
-    if (any) jag_issue<T, LC>(X0, c, CPG * LC, cum[i], a);
+    if (any) jag_issue<T, TS, LC>(X0, c, CPG * LC, cum[i], a);
     return any;
   };
   auto overflow = [&](int i, const T* win, T acc) {
@@ -497,21 +503,21 @@ __global__ __launch_bounds__(kJagNT, 1) void k_jag_pass(JagArgs a, Src src, Epi 
     int k0 = CPG * LC;
     if constexpr (!kOvfPipe) {
       while (__ballot(c > k0) != 0ull) {
-        jag_issue<T, LC>(X0, c, k0, cum[i], a);
-        acc = jag_consume<T, LC>(X0, c, k0, win, acc);
+        jag_issue<T, TS, LC>(X0, c, k0, cum[i], a);
+        acc = jag_consume<T, TS, LC>(X0, c, k0, win, acc);
         k0 += LC;
       }
       return acc;
     }
     for (;;) {
       const bool m1 = __ballot(c > k0 + LC) != 0ull;
-      if (m1) jag_issue<T, LC>(X1, c, k0 + LC, cum[i], a);
-      acc = jag_consume<T, LC>(X0, c, k0, win, acc);
+      if (m1) jag_issue<T, TS, LC>(X1, c, k0 + LC, cum[i], a);
+      acc = jag_consume<T, TS, LC>(X0, c, k0, win, acc);
       k0 += LC;
       if (!m1) break;
       const bool m2 = __ballot(c > k0 + LC) != 0ull;
-      if (m2) jag_issue<T, LC>(X0, c, k0 + LC, cum[i], a);
-      acc = jag_consume<T, LC>(X1, c, k0, win, acc);
+      if (m2) jag_issue<T, TS, LC>(X0, c, k0 + LC, cum[i], a);
+      acc = jag_consume<T, TS, LC>(X1, c, k0, win, acc);
       k0 += LC;
       if (!m2) break;
     }
@@ -536,12 +542,12 @@ __global__ __launch_bounds__(kJagNT, 1) void k_jag_pass(JagArgs a, Src src, Epi 
       if (q + 1 < Q) {
         const int i1 = (q + 1) / CPG, ch1 = (q + 1) % CPG;
         const int c1 = jag_count<CB>(cw, i1);
-        if (ch1 < kJagCPGU || __ballot(c1 > ch1 * LC) != 0ull) jag_issue<T, LC>(C[(q + 1) & 1], c1, ch1 * LC, cum[i1], a);
+        if (ch1 < kJagCPGU || __ballot(c1 > ch1 * LC) != 0ull) jag_issue<T, TS, LC>(C[(q + 1) & 1], c1, ch1 * LC, cum[i1], a);
         if (ch1 == 0) pre[i1 & 1] = pre_of(i1);
       }
       const bool ovf = ch == CPG - 1 && overflow_issue(i);
       const int ci = jag_count<CB>(cw, i);
-      if (ch < kJagCPGU || __ballot(ci > ch * LC) != 0ull) acc = jag_consume<T, LC>(C[q & 1], ci, ch * LC, win, acc);
+      if (ch < kJagCPGU || __ballot(ci > ch * LC) != 0ull) acc = jag_consume<T, TS, LC>(C[q & 1], ci, ch * LC, win, acc);
       if (ch == CPG - 1) {
         if (ovf) acc = overflow(i, win, acc);
         const int r = row_of(i);
@@ -552,7 +558,7 @@ __global__ __launch_bounds__(kJagNT, 1) void k_jag_pass(JagArgs a, Src src, Epi 
     }
     KRCN_JAG_WAVE_STAMP(16 + wave);
     KRCN_JAG_STAMP(3);
-    if (a.nlong > 0) red += jag_long_rows<T, Epi>(a, epi, win, reinterpret_cast<T*>(win_raw + a.lpiece), b, wave, lane, jl);
+    if (a.nlong > 0) red += jag_long_rows<T, TS, Epi>(a, epi, win, reinterpret_cast<T*>(win_raw + a.lpiece), b, wave, lane, jl);
   }
   if constexpr (Epi::kReduce) jag_block_red(red, reinterpret_cast<double*>(win_raw), sm, partials, epi, b);
   KRCN_JAG_STAMP(10);
@@ -603,7 +609,7 @@ __device__ __forceinline__ void jag_row_starts(const CW& cw, unsigned (&rs)[(K +
 #ifndef KRCN_JAG_LAG
 #define KRCN_JAG_LAG 1   // units between a window piece's fetch and its LDS store (A/B: variant builds)
 #endif
-template <typename T, int K, class Src, class Epi>
+template <typename T, typename TS, int K, class Src, class Epi>
 __global__ __launch_bounds__(kJagNT, 1) void k_jag_acc(JagArgs a, Src src, Epi epi, double* __restrict__ partials) {
   constexpr int R = JagGeom<T>::kR2;
   constexpr int NP = JagGeom<T>::kPieces2;
@@ -611,7 +617,8 @@ __global__ __launch_bounds__(kJagNT, 1) void k_jag_acc(JagArgs a, Src src, Epi e
   constexpr int kZero = kJagSlab;          // a zero slot past every wave's slab
   // one 8-bit count per unit: a 32-bit word for K <= 4, 64-bit for K <= 8
   typedef typename std::conditional<K <= 4, unsigned, unsigned long long>::type CW;
-  typedef typename JagPair<T>::type T2;
+  typedef typename JagPair<T>::type T2;     // a slab entry: two products
+  typedef typename JagPair<TS>::type TS2;   // a lane's two stored values
   static_assert(K <= 8, "lane counts of K units must fit one 64-bit word");
   __shared__ double sm[kJagWaves];
   __shared__ u32x4 win_raw[2 * NP];
@@ -625,7 +632,7 @@ __global__ __launch_bounds__(kJagNT, 1) void k_jag_acc(JagArgs a, Src src, Epi e
   const T* slab = reinterpret_cast<const T*>(slab2);
   if (lane == 0) slab2[kJagSlab / 2] = T2{};   // the zero slot (never written again)
   const unsigned short* __restrict__ widx = a.widx;
-  const T* __restrict__ wval = static_cast<const T*>(a.wval);
+  const TS* __restrict__ wval = static_cast<const TS*>(a.wval);
   // slice metadata (clamped to the last slice: loads stay unconditional)
   auto meta = [&](int s, CW& cw, int& bv) {
     s = s < a.S ? s : a.S - 1;
@@ -635,18 +642,18 @@ __global__ __launch_bounds__(kJagNT, 1) void k_jag_acc(JagArgs a, Src src, Epi e
   };
   // lanes past the unit's elements load its first pair (a line the wave
   // fetches anyway): no over-fetch
-  auto issue = [&](JagUnit<T>& U, int i, int bv) {
+  auto issue = [&](JagUnit<TS>& U, int i, int bv) {
     const unsigned e0 = unsigned(__builtin_amdgcn_readlane(bv, i));
     const int n = __builtin_amdgcn_readlane(bv, K + i);
     const unsigned p = 2 * lane < n ? e0 + 2u * unsigned(lane) : e0;
     U.o = KRCN_STREAM_LOAD(reinterpret_cast<const u16x2*>(widx + p));
-    U.v = KRCN_STREAM_LOAD(reinterpret_cast<const T2*>(wval + p));
+    U.v = KRCN_STREAM_LOAD(reinterpret_cast<const TS2*>(wval + p));
   };
   CW cw0, cw1;
   int bv0, bv1;
   meta(0, cw0, bv0);
   meta(1, cw1, bv1);
-  JagUnit<T> U[K];
+  JagUnit<TS> U[K];
 #pragma unroll
   for (int i = 0; i < K; ++i) issue(U[i], i, bv0);
   {
@@ -688,8 +695,8 @@ __global__ __launch_bounds__(kJagNT, 1) void k_jag_acc(JagArgs a, Src src, Epi e
       const int c = int(cw0 >> (8 * i)) & 0xff;
       const int rs = int(rsw[i / 4] >> (8 * (i % 4))) & 0xff;
       T2 pr;
-      pr.x = U[i].v.x * win[U[i].o.x];
-      pr.y = U[i].v.y * win[U[i].o.y];
+      pr.x = T(U[i].v.x) * win[U[i].o.x];
+      pr.y = T(U[i].v.y) * win[U[i].o.y];
       slab2[lane] = pr;
       wave_lds_sync();
       // a lane's levels past its count read the zero slot: adding +0.0 leaves
@@ -808,16 +815,16 @@ __global__ __launch_bounds__(kJagNT, 1) void k_jag_acc(JagArgs a, Src src, Epi e
 
 // Long rows' elements into their own arrays (row i at lbeg[i], CSR order;
 // the arrays are zeroed first, so each row's even padding holds zeros).
-template <typename T>
+template <typename T, typename TS>
 __global__ __launch_bounds__(kNT) void k_jag_long_fill(int nl, int W, const int* __restrict__ lrow,
                                                        const int* __restrict__ lbeg, const int* __restrict__ ptr,
                                                        const int* __restrict__ idx, const T* __restrict__ val,
-                                                       unsigned short* __restrict__ lidx, T* __restrict__ lval) {
+                                                       unsigned short* __restrict__ lidx, TS* __restrict__ lval) {
   for (int i = blockIdx.x; i < nl; i += gridDim.x) {
     const int r = lrow[i], e0 = ptr[r], len = ptr[r + 1] - e0;
     for (int k = threadIdx.x; k < len; k += kNT) {
       lidx[lbeg[i] + k] = static_cast<unsigned short>(idx[e0 + k] % W);
-      lval[lbeg[i] + k] = val[e0 + k];
+      lval[lbeg[i] + k] = static_cast<TS>(val[e0 + k]);
     }
   }
 }
@@ -834,12 +841,12 @@ __global__ __launch_bounds__(kNT) void k_jag_long_fill(int nl, int W, const int*
 // Elements into place: sorted position p of unit u lands at p (pbase null) or
 // at pbase[u] + (p - first[u]) (units padded to even element counts); sorted
 // items past the real nonzeros (perm >= nnz) are pads: offset 0, value 0.
-template <typename T>
+template <typename T, typename TS>
 __global__ __launch_bounds__(kNT) void k_jag_gather(int64_t n, int64_t nnz, int W, const int* __restrict__ perm,
                                                     const int* __restrict__ idx, const T* __restrict__ val,
                                                     const unsigned long long* __restrict__ keys,
                                                     const int* __restrict__ first, const int* __restrict__ pbase,
-                                                    unsigned short* __restrict__ widx, T* __restrict__ wval) {
+                                                    unsigned short* __restrict__ widx, TS* __restrict__ wval) {
   for (int64_t p = int64_t(blockIdx.x) * kNT + threadIdx.x; p < n; p += int64_t(gridDim.x) * kNT) {
     const int e = perm[p];
     int64_t q = p;
@@ -849,7 +856,7 @@ __global__ __launch_bounds__(kNT) void k_jag_gather(int64_t n, int64_t nnz, int 
     }
     const bool real = e < nnz;
     widx[q] = real ? static_cast<unsigned short>(idx[e] % W) : static_cast<unsigned short>(0);
-    wval[q] = real ? val[e] : T(0);
+    wval[q] = real ? static_cast<TS>(val[e]) : TS(0);
   }
 }
 

@@ -126,6 +126,20 @@ inline void launch_sorted(const PassPlan& P, const Src& first, const E& ep, doub
   });
 }
 
+// f(a value of the plan's stored value type): T, or float for a narrowed plan
+// of an fp64 handle (PassPlan::vbytes == 4).  Only T = double gets the second
+// instantiation.
+template <typename T, class F>
+inline void with_stored(const PassPlan& P, F&& f) {
+  if constexpr (std::is_same<T, double>::value) {
+    if (P.vbytes == 4) {
+      f(0.0f);
+      return;
+    }
+  }
+  f(T(0));
+}
+
 // Both window kinds: the slices kernel writes per-slice partials (mode 0; the
 // fused step B of an IsLzZ source: mode 2), the accumulate kernel (mode 1)
 // runs the caller's epilogue.
@@ -135,13 +149,16 @@ inline void launch_window(const PassPlan& P, const Src& first, const E& ep, doub
   WinArgs wa{P.rows, P.W, P.stride, P.S, IsLzZ<Src>::value ? 2 : (accum ? 1 : 0), P.ntiles, P.cols,
              P.tb, P.ro, P.widx, P.val, P.segs};
   wa.kpb = P.kpb;
-  auto launch = [&](auto rc) {
-    hipLaunchKernelGGL((k_window_pass<T, decltype(rc)::value, Src, E, accum>), dim3(P.grid), dim3(kWinNT), 0, s, wa,
-                       first, ep, parts);
-  };
-  if (P.R == 16) launch(std::integral_constant<int, 16>{});
-  else if (P.R == 32) launch(std::integral_constant<int, 32>{});
-  else launch(std::integral_constant<int, 64>{});
+  with_stored<T>(P, [&](auto ts) {
+    using TS = decltype(ts);
+    auto launch = [&](auto rc) {
+      hipLaunchKernelGGL((k_window_pass<T, TS, decltype(rc)::value, Src, E, accum>), dim3(P.grid), dim3(kWinNT), 0, s,
+                         wa, first, ep, parts);
+    };
+    if (P.R == 16) launch(std::integral_constant<int, 16>{});
+    else if (P.R == 32) launch(std::integral_constant<int, 32>{});
+    else launch(std::integral_constant<int, 64>{});
+  });
 }
 
 // Single window (S == 1): k_jag_pass.  Accumulate over jG slice groups:
@@ -162,29 +179,32 @@ inline void launch_jag(const PassPlan& P, const Src& first, const E& ep, double*
     ja.lidx = P.jlidx;
     ja.lval = P.jlval;
   }
-  if constexpr (!std::is_same<E, EpiSlicePart<T>>::value) {
-    if (P.S == 1) {
-      auto one = [&](auto kc) {
-        constexpr int K = decltype(kc)::value;
-        hipLaunchKernelGGL((k_jag_pass<T, K, jag_cpg(K), 8, Src, E>), dim3(P.grid), dim3(kJagNT), 0, s, ja, first, ep,
-                           parts);
-      };
-      if (P.jK == 1) one(std::integral_constant<int, 1>{});
-      else if (P.jK == 2) one(std::integral_constant<int, 2>{});
-      else if (P.jK == 3) one(std::integral_constant<int, 3>{});
-      else one(std::integral_constant<int, kJagK1>{});
-      return;
+  with_stored<T>(P, [&](auto ts) {
+    using TS = decltype(ts);
+    if constexpr (!std::is_same<E, EpiSlicePart<T>>::value) {
+      if (P.S == 1) {
+        auto one = [&](auto kc) {
+          constexpr int K = decltype(kc)::value;
+          hipLaunchKernelGGL((k_jag_pass<T, TS, K, jag_cpg(K), 8, Src, E>), dim3(P.grid), dim3(kJagNT), 0, s, ja, first,
+                             ep, parts);
+        };
+        if (P.jK == 1) one(std::integral_constant<int, 1>{});
+        else if (P.jK == 2) one(std::integral_constant<int, 2>{});
+        else if (P.jK == 3) one(std::integral_constant<int, 3>{});
+        else one(std::integral_constant<int, kJagK1>{});
+        return;
+      }
     }
-  }
-  if (P.jK == 4)
-    hipLaunchKernelGGL((k_jag_acc<T, 4, Src, E>), dim3(P.grid), dim3(kJagNT), 0, s, ja, first, ep, parts);
-  else
-    hipLaunchKernelGGL((k_jag_acc<T, kJagK2, Src, E>), dim3(P.grid), dim3(kJagNT), 0, s, ja, first, ep, parts);
+    if (P.jK == 4)
+      hipLaunchKernelGGL((k_jag_acc<T, TS, 4, Src, E>), dim3(P.grid), dim3(kJagNT), 0, s, ja, first, ep, parts);
+    else
+      hipLaunchKernelGGL((k_jag_acc<T, TS, kJagK2, Src, E>), dim3(P.grid), dim3(kJagNT), 0, s, ja, first, ep, parts);
+  });
 }
 
 template <typename T, class Src, class E>
 inline void launch_dense(const PassPlan& P, const Src& first, const E& ep, double* parts, hipStream_t s) {
-  DenseArgs da{P.rows, P.S, P.ntiles, P.cols, P.dld, P.dld / int64_t(16 / P.dvs), P.val};
+  DenseArgs da{P.rows, P.S, P.ntiles, P.cols, P.dld, P.dld / int64_t(16 / P.vbytes), P.val};
   auto launch = [&](auto ts) {   // ts: a value of the image's stored type
     using TS = decltype(ts);
     with_lanes(P.L, [&](auto lc) {
@@ -192,7 +212,7 @@ inline void launch_dense(const PassPlan& P, const Src& first, const E& ep, doubl
                          first, ep, parts);
     });
   };
-  if (P.dvs == int(sizeof(T))) launch(T(0));
+  if (P.vbytes == int(sizeof(T))) launch(T(0));
   else launch(0.0f);   // fp32 values under fp64 arithmetic (KRCN_VALUES_F32)
 }
 
@@ -237,10 +257,13 @@ inline krcn_status run_pass(PassPlan& P, const Src& first, const Src2& rest, con
     // are never selected for one (lanczos_impl: fuse, fuse_u and early need a
     // window, sorted or jagged pass 1)
     if (z || u) return fail(KRCN_ERR_UNSUPPORTED, "fused Lanczos steps do not run over a dense plan");
-    if (P.dvs != int(sizeof(T)) && P.dvs != 4)
-      return fail(KRCN_ERR_INVALID, "run_pass: a dense plan with %d-byte values under %d-byte arithmetic", P.dvs,
-                  int(sizeof(T)));
   }
+  // the stored width of the plan's values: the arithmetic's, or fp32 under
+  // fp64 arithmetic in the kinds that narrow (with_stored, launch_dense)
+  if (P.vbytes != int(sizeof(T)) &&
+      (P.vbytes != 4 || kind == KRCN_PLAN_WAVE || kind == KRCN_PLAN_SORTED))
+    return fail(KRCN_ERR_INVALID, "run_pass: a plan of kind %d with %d-byte values under %d-byte arithmetic", kind,
+                P.vbytes, int(sizeof(T)));
   if constexpr (u) {
     if (kind != KRCN_PLAN_JAG || P.S != 1)
       return fail(KRCN_ERR_UNSUPPORTED, "the two-launch Lanczos pass 2 needs a single-window jagged plan");
@@ -320,14 +343,15 @@ inline krcn_status run_pass(PassPlan& P, const Src& first, const Src2& rest, con
 // folded in (krcn_window.hpp EpiSliceFold; tuning builds).
 inline bool fold_ok(const krcn_csr* h) {
   const PassPlan& P = h->p1;
-  return h->fcnt && P.kind == KRCN_PLAN_WINDOW_SLICES && P.R == 32 && P.S <= 96 && P.ntiles <= h->pcap;
+  return h->fcnt && P.kind == KRCN_PLAN_WINDOW_SLICES && P.R == 32 && P.S <= 96 && P.ntiles <= h->pcap &&
+         P.vbytes == int(h->vs);   // (full-width plans only)
 }
 template <typename T>
 inline krcn_status run_fold_pass1(krcn_csr* h, const SrcLzBeta<T>& src, const EpiSliceFold<T>& epi, hipStream_t s) {
   PassPlan& P = h->p1;
   WinArgs wa{P.rows, P.W, P.stride, P.S, 0, P.ntiles, P.cols, P.tb, P.ro, P.widx, P.val, P.segs};
   wa.kpb = P.kpb;
-  hipLaunchKernelGGL((k_window_pass<T, 32, SrcLzBeta<T>, EpiSliceFold<T>, false>), dim3(P.grid), dim3(kWinNT), 0, s,
+  hipLaunchKernelGGL((k_window_pass<T, T, 32, SrcLzBeta<T>, EpiSliceFold<T>, false>), dim3(P.grid), dim3(kWinNT), 0, s,
                      wa, src, epi, static_cast<double*>(nullptr));
   LAUNCHCHK();
   return KRCN_OK;

@@ -17,12 +17,14 @@ void free_plan(PassPlan& P) {
   static_cast<PlanFields&>(P) = PlanFields();
 }
 
-// An empty plan of the given shape: what every builder starts from.
-static void reset_plan(PassPlan& P, int rows, int64_t cols, int64_t nnz) {
+// An empty plan of the given shape: what every builder starts from (vs: the
+// handle's value size; a builder that narrows its values sets P.vbytes itself).
+static void reset_plan(PassPlan& P, int rows, int64_t cols, int64_t nnz, size_t vs) {
   free_plan(P);
   P.rows = rows;
   P.cols = cols;
   P.nnz = nnz;
+  P.vbytes = int(vs);
 }
 
 // Cut [0, n) into B ranges of equal weight by the prefix sums pre[0 .. n]:
@@ -47,7 +49,9 @@ static int slices_for(int64_t bytes) {
 
 // Sliced copy of a CSR: slice s holds columns [bounds[s], bounds[s+1]) with
 // global column ids, rows in order; row pointers flattened slice-major.
-template <typename T>
+// The values are stored as TS (static_cast<TS>(v); T but for a narrowed
+// window plan).
+template <typename T, typename TS = T>
 static krcn_status build_slices(PassPlan& P, const int* ptr, const int* idx, const T* val, hipStream_t s,
                                 const std::vector<int>* bounds_in = nullptr, int64_t pad = 0) {
   const int S = P.S, rows = P.rows;
@@ -60,8 +64,8 @@ static krcn_status build_slices(PassPlan& P, const int* ptr, const int* idx, con
   const size_t nptr = size_t(S) * rows + 1;
   CHK(P.own.alloc(&P.own_ptr, sizeof(int) * nptr));
   CHK(P.own.alloc(&P.own_idx, sizeof(int) * std::max<int64_t>(nnz, 1)));
-  CHK(P.own.alloc(&P.own_val, sizeof(T) * size_t(std::max<int64_t>(nnz, 1) + pad)));
-  if (pad) HIPCHK(hipMemsetAsync(static_cast<T*>(P.own_val) + nnz, 0, sizeof(T) * size_t(pad), s));
+  CHK(P.own.alloc(&P.own_val, sizeof(TS) * size_t(std::max<int64_t>(nnz, 1) + pad)));
+  if (pad) HIPCHK(hipMemsetAsync(static_cast<TS*>(P.own_val) + nnz, 0, sizeof(TS) * size_t(pad), s));
   CHK(counts.alloc(sizeof(int) * nptr));
   HIPCHK(hipMemsetAsync(counts.p, 0, sizeof(int) * nptr, s));
   if (nnz > 0) {
@@ -83,8 +87,8 @@ static krcn_status build_slices(PassPlan& P, const int* ptr, const int* idx, con
     HIPCHK(hipcub::DeviceRadixSort::SortPairs(tmp.p, tmpb, sid.p, sid_out.p, iota.p, perm.p, int(nnz), 0, bits, s));
     hipLaunchKernelGGL(k_slice_counts, dim3(vec_grid(int64_t(rows) * 64)), dim3(kNT), 0, s, rows, ptr, sid.p, counts.p);
     LAUNCHCHK();
-    hipLaunchKernelGGL((k_slice_gather<T>), dim3(vec_grid(nnz)), dim3(kNT), 0, s, nnz, perm.p, idx, val,
-                       P.own_idx, static_cast<T*>(P.own_val));
+    hipLaunchKernelGGL((k_slice_gather<T, TS>), dim3(vec_grid(nnz)), dim3(kNT), 0, s, nnz, perm.p, idx, val,
+                       P.own_idx, static_cast<TS*>(P.own_val));
     LAUNCHCHK();
     size_t tmp2 = 0;
     HIPCHK(hipcub::DeviceScan::InclusiveSum(nullptr, tmp2, counts.p, P.own_ptr, int(nptr), s));
@@ -393,17 +397,20 @@ static int window_choice(int rows, int64_t cols, int64_t nnz, size_t vs) {
 // of X^T u (EpiLz1X, krcn_window.hpp).  Every column's run (rows ascending) is
 // padded to whole chunks of kXtChunk (value 0, row kXtPad); xcp holds per
 // block the cols + 1 absolute chunk ids.  Skipped (P.xt = 0) when a block's
-// chunk sums do not fit the LDS past the window and its rows.
-template <typename T>
+// chunk sums do not fit the LDS past the window and its rows.  The copy is made
+// from the plan's own values (stored as TS) and holds them widened to T: under
+// narrowed storage X^T u runs over the same rounded matrix as X z, in 8-byte
+// entries (EpiLz1X and k_xt_combine are the full-width code).
+template <typename T, typename TS>
 static krcn_status build_xt(PassPlan& P, const std::vector<int>& hp, const std::vector<int>& cut, int B,
                             hipStream_t s) {
   const int rows = P.rows, R = P.R, cols = int(P.cols);
   const int64_t nnz = P.nnz;
   std::vector<unsigned short> hidx(size_t(std::max<int64_t>(nnz, 1)));
-  std::vector<T> hval(size_t(std::max<int64_t>(nnz, 1)));
+  std::vector<TS> hval(size_t(std::max<int64_t>(nnz, 1)));
   if (nnz > 0) {
     HIPCHK(hipMemcpy(hidx.data(), P.widx, sizeof(unsigned short) * size_t(nnz), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(hval.data(), P.val, sizeof(T) * size_t(nnz), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(hval.data(), P.val, sizeof(TS) * size_t(nnz), hipMemcpyDeviceToHost));
   }
   const size_t ncp = size_t(B) * (size_t(cols) + 1);
   std::vector<int> cp(ncp);
@@ -435,7 +442,7 @@ static krcn_status build_xt(PassPlan& P, const std::vector<int>& hp, const std::
       for (int e = hp[r]; e < hp[r + 1]; ++e) {
         const int64_t k = pos[hidx[size_t(e)]]++;
         xr[size_t(k)] = static_cast<unsigned short>(r - r0);
-        xv[size_t(k)] = hval[size_t(e)];
+        xv[size_t(k)] = T(hval[size_t(e)]);
       }
   }
   const size_t ne = std::max<size_t>(xr.size(), kXtChunk);
@@ -453,10 +460,13 @@ static krcn_status build_xt(PassPlan& P, const std::vector<int>& hp, const std::
   return KRCN_OK;
 }
 
-template <typename T>
-static krcn_status build_window(PassPlan& P, const int* ptr, const int* idx, const T* val, int accum,
-                                hipStream_t s) {
+// TS: the stored type of the values.  The geometry (slices, tiles, segments,
+// grids) is T's whatever TS is: only the element type of own_val changes.
+template <typename T, typename TS>
+static krcn_status build_window_as(PassPlan& P, const int* ptr, const int* idx, const T* val, int accum,
+                                   hipStream_t s) {
   const int64_t Wmax = WinGeom<T>::kW;
+  P.vbytes = int(sizeof(TS));
   const int rows = P.rows;
   const int64_t cols = P.cols, nnz = P.nnz;
   int S = 1, kpb = 1;
@@ -473,7 +483,7 @@ static krcn_status build_window(PassPlan& P, const int* ptr, const int* idx, con
   P.groups = 1;
   std::vector<int> hb(S + 1);
   for (int k = 0; k <= S; ++k) hb[k] = int(std::min<int64_t>(int64_t(k) * W, cols));
-  CHK(build_slices<T>(P, ptr, idx, val, s, &hb, kWinPad));
+  CHK((build_slices<T, TS>(P, ptr, idx, val, s, &hb, kWinPad)));
   CHK(P.own.alloc(&P.widx, sizeof(unsigned short) * size_t(nnz + kWinPad)));
   HIPCHK(hipMemsetAsync(P.widx, 0, sizeof(unsigned short) * size_t(nnz + kWinPad), s));
   if (nnz > 0) {
@@ -556,7 +566,7 @@ static krcn_status build_window(PassPlan& P, const int* ptr, const int* idx, con
             WinSeg{sl, cut[b], cut[b + 1], kSegLoad | (sl == S - 1 ? kSegFlush : 0) | (sl == 0 ? S << 8 : 0)};
     }
     P.grid = B;
-    if (S == 1 && cols <= kWinNT) CHK(build_xt<T>(P, hp, cut, B, s));
+    if (S == 1 && cols <= kWinNT) CHK((build_xt<T, TS>(P, hp, cut, B, s)));
   } else {
     P.stride = 1;
     P.grid = S * kpb;
@@ -583,6 +593,14 @@ static krcn_status build_window(PassPlan& P, const int* ptr, const int* idx, con
   if (!segs.empty())
     HIPCHK(hipMemcpy(P.segs, segs.data(), sizeof(WinSeg) * segs.size(), hipMemcpyHostToDevice));
   return KRCN_OK;
+}
+
+template <typename T>
+static krcn_status build_window(PassPlan& P, const int* ptr, const int* idx, const T* val, int accum, size_t vs,
+                                hipStream_t s) {
+  if constexpr (std::is_same<T, double>::value)
+    if (vs == 4) return build_window_as<T, float>(P, ptr, idx, val, accum, s);
+  return build_window_as<T, T>(P, ptr, idx, val, accum, s);
 }
 
 // ------------------------------------------------------ jagged plans
@@ -693,10 +711,13 @@ static bool jag_choice(int rows, int64_t cols, int64_t nnz, int pass) {
   return mat >= 0.25 * win;
 }
 
-template <typename T>
-static krcn_status build_jag(PassPlan& P, const int* ptr, const int* idx, const T* val, int pass, bool seq,
-                             hipStream_t s) {
+// TS: the stored type of the values (own_val and the long rows' jlval).  Every
+// choice below (slices, groups, K, the long-row rule, the grid) is T's.
+template <typename T, typename TS>
+static krcn_status build_jag_as(PassPlan& P, const int* ptr, const int* idx, const T* val, int pass, bool seq,
+                                hipStream_t s) {
   const int rows = P.rows;
+  P.vbytes = int(sizeof(TS));
   const int64_t cols = P.cols, nnz = P.nnz;
   if (cols < JagGeom<T>::kE || rows == 0 || nnz == 0)
     return fail(KRCN_ERR_UNSUPPORTED, "jag plan: empty or too narrow (%lld columns)", (long long)cols);
@@ -913,11 +934,11 @@ static krcn_status build_jag(PassPlan& P, const int* ptr, const int* idx, const 
     LAUNCHCHK();
   }
   CHK(P.own.alloc(&P.widx, sizeof(unsigned short) * size_t(total + kJagPad)));
-  CHK(P.own.alloc(&P.own_val, sizeof(T) * size_t(total + kJagPad)));
+  CHK(P.own.alloc(&P.own_val, sizeof(TS) * size_t(total + kJagPad)));
   HIPCHK(hipMemsetAsync(P.widx, 0, sizeof(unsigned short) * size_t(total + kJagPad), s));
-  HIPCHK(hipMemsetAsync(P.own_val, 0, sizeof(T) * size_t(total + kJagPad), s));
-  hipLaunchKernelGGL((k_jag_gather<T>), dim3(vec_grid(pairs ? total : nnz)), dim3(kNT), 0, s, pairs ? total : nnz,
-                     nnz, W, perm.p, idx, val, keys_out.p, first.p, pbase.p, P.widx, static_cast<T*>(P.own_val));
+  HIPCHK(hipMemsetAsync(P.own_val, 0, sizeof(TS) * size_t(total + kJagPad), s));
+  hipLaunchKernelGGL((k_jag_gather<T, TS>), dim3(vec_grid(pairs ? total : nnz)), dim3(kNT), 0, s, pairs ? total : nnz,
+                     nnz, W, perm.p, idx, val, keys_out.p, first.p, pbase.p, P.widx, static_cast<TS*>(P.own_val));
   LAUNCHCHK();
   hipLaunchKernelGGL(k_jag_umeta, dim3(vec_grid(nrec * 2 * K)), dim3(kNT), 0, s, nrec, K, pbase.p ? pbase.p : first.p,
                      usize.p, P.jumeta);
@@ -931,7 +952,7 @@ static krcn_status build_jag(PassPlan& P, const int* ptr, const int* idx, const 
     CHK(P.own.alloc(&P.jltask, sizeof(int) * ltask.size()));
     CHK(P.own.alloc(&P.jtask, sizeof(int) * tasks.size()));
     CHK(P.own.alloc(&P.jlidx, sizeof(unsigned short) * lsz));
-    CHK(P.own.alloc(&P.jlval, sizeof(T) * lsz));
+    CHK(P.own.alloc(&P.jlval, sizeof(TS) * lsz));
     DevTmp<int> lbeg_d;
     CHK(lbeg_d.alloc(sizeof(int) * size_t(nl)));
     HIPCHK(hipMemcpyAsync(P.jlcut, lcut.data(), sizeof(int) * lcut.size(), hipMemcpyHostToDevice, s));
@@ -940,9 +961,9 @@ static krcn_status build_jag(PassPlan& P, const int* ptr, const int* idx, const 
     HIPCHK(hipMemcpyAsync(P.jtask, tasks.data(), sizeof(int) * tasks.size(), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(lbeg_d.p, lbeg.data(), sizeof(int) * size_t(nl), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemsetAsync(P.jlidx, 0, sizeof(unsigned short) * lsz, s));
-    HIPCHK(hipMemsetAsync(P.jlval, 0, sizeof(T) * lsz, s));
-    hipLaunchKernelGGL((k_jag_long_fill<T>), dim3(std::min(nl, 4096)), dim3(kNT), 0, s, nl, W, P.jlrow, lbeg_d.p, ptr,
-                       idx, val, P.jlidx, static_cast<T*>(P.jlval));
+    HIPCHK(hipMemsetAsync(P.jlval, 0, sizeof(TS) * lsz, s));
+    hipLaunchKernelGGL((k_jag_long_fill<T, TS>), dim3(std::min(nl, 4096)), dim3(kNT), 0, s, nl, W, P.jlrow, lbeg_d.p, ptr,
+                       idx, val, P.jlidx, static_cast<TS*>(P.jlval));
     LAUNCHCHK();
     HIPCHK(hipStreamSynchronize(s));
     lbeg_d.reset();
@@ -975,6 +996,14 @@ static krcn_status build_jag(PassPlan& P, const int* ptr, const int* idx, const 
   return KRCN_OK;
 }
 
+template <typename T>
+static krcn_status build_jag(PassPlan& P, const int* ptr, const int* idx, const T* val, int pass, bool seq, size_t vs,
+                             hipStream_t s) {
+  if constexpr (std::is_same<T, double>::value)
+    if (vs == 4) return build_jag_as<T, float>(P, ptr, idx, val, pass, seq, s);
+  return build_jag_as<T, T>(P, ptr, idx, val, pass, seq, s);
+}
+
 // ----------------------------------------------------------- dense format
 // The image of one pass (krcn_dense.hpp): zero fill plus a scatter of the CSR
 // on the build stream; the slice partials when the geometry slices the pass.
@@ -996,7 +1025,7 @@ static krcn_status build_dense_as(PassPlan& P, const int* ptr, const int* idx, c
   HIPCHK(hipStreamSynchronize(s));
   P.kind = KRCN_PLAN_DENSE;
   P.dld = g.ld;
-  P.dvs = int(sizeof(TS));
+  P.vbytes = int(sizeof(TS));
   P.S = g.S;
   P.L = g.L;
   P.ntiles = int(g.groups);
@@ -1025,10 +1054,11 @@ __global__ __launch_bounds__(256) void k_values_f32_exact(const double* __restri
   if (bad) atomicOr(flag, 1);
 }
 
-// Bytes per stored value of the dense images a plan build is about to make:
-// the handle's policy (krcn_csr_set_value_storage), decided once per build.
+// Bytes per stored value of the passes a plan build may narrow (dense, window
+// and jagged plans): the handle's policy (krcn_csr_set_value_storage), decided
+// once per build.
 template <typename T>
-static krcn_status dense_value_bytes(const krcn_csr* h, hipStream_t s, size_t* vs) {
+static krcn_status stored_value_bytes(const krcn_csr* h, hipStream_t s, size_t* vs) {
   *vs = sizeof(T);
   if (sizeof(T) == 4 || h->values == KRCN_VALUES_FULL) return KRCN_OK;
   if (h->values == KRCN_VALUES_F32_EXACT && h->nnz > 0) {
@@ -1084,23 +1114,25 @@ extern "C" krcn_status krcn_dense_geometry(int64_t rows, int64_t cols, int dtype
 
 template <typename T>
 static krcn_status build_plan(krcn_csr* h, int pass, int rows, int64_t cols, int64_t nnz, const int* ptr,
-                              const int* idx, const T* val, int lanes, hipStream_t s) {
+                              const int* idx, const T* val, int lanes, size_t csr_vs, hipStream_t s) {
+  // csr_vs: bytes per stored value of a window or jagged plan (build_plans:
+  // sizeof(T), or the build's stored width when the other pass narrows too)
   PassPlan& P = pass == 2 ? h->p2 : h->p1;
-  reset_plan(P, rows, cols, nnz);
+  reset_plan(P, rows, cols, nnz, sizeof(T));
   const bool seq = lanes == KRCN_LANES_SEQUENTIAL;
   const int fmt = pass_format(h, pass);
   if (fmt == KRCN_FORMAT_DENSE) {
     if (h->shard != KRCN_SHARD_NONE)
       return fail(KRCN_ERR_UNSUPPORTED, "the dense format does not run on a sharded handle");
-    return build_dense<T>(P, ptr, idx, val, lanes, h->slicing, h->dense_vs, s);
+    return build_dense<T>(P, ptr, idx, val, lanes, h->slicing, h->store_vs, s);
   }
   // jagged format: forced, or by the auto policy (its summation order is
   // scipy's, so the sequential lane policy may use it too)
   if (fmt == KRCN_FORMAT_JAG ||
       (fmt == KRCN_FORMAT_AUTO && h->slicing == KRCN_SLICING_AUTO && jag_choice<T>(rows, cols, nnz, pass))) {
-    const krcn_status r = build_jag<T>(P, ptr, idx, val, pass, seq, s);
+    const krcn_status r = build_jag<T>(P, ptr, idx, val, pass, seq, csr_vs, s);
     if (r != KRCN_ERR_UNSUPPORTED || fmt == KRCN_FORMAT_JAG) return r;
-    reset_plan(P, rows, cols, nnz);
+    reset_plan(P, rows, cols, nnz, sizeof(T));
   }
   // LDS-window format: forced, or by the auto policy (never under the
   // sequential lane policy, whose sliced passes must stay unsliced)
@@ -1113,9 +1145,9 @@ static krcn_status build_plan(krcn_csr* h, int pass, int rows, int64_t cols, int
       wc = window_choice(rows, cols, nnz, sizeof(T));
     }
     if (wc) {
-      const krcn_status r = build_window<T>(P, ptr, idx, val, wc == 1, s);
+      const krcn_status r = build_window<T>(P, ptr, idx, val, wc == 1, csr_vs, s);
       if (r != KRCN_ERR_UNSUPPORTED || fmt == KRCN_FORMAT_WINDOW) return r;
-      reset_plan(P, rows, cols, nnz);   // not applicable to this matrix: fall through to the other formats
+      reset_plan(P, rows, cols, nnz, sizeof(T));   // not applicable to this matrix: fall through to the other formats
     }
   }
   // format
@@ -1203,17 +1235,24 @@ static krcn_status build_plan(krcn_csr* h, int pass, int rows, int64_t cols, int
   return KRCN_OK;
 }
 
+// The plan kinds that honour the handle's value storage policy.
+static bool plan_narrows(int kind) {
+  return kind == KRCN_PLAN_DENSE || kind == KRCN_PLAN_WINDOW_SLICES || kind == KRCN_PLAN_WINDOW_ACCUM ||
+         kind == KRCN_PLAN_JAG;
+}
+
 template <typename T>
 static krcn_status build_plans(krcn_csr* h, bool lz2, hipStream_t s) {
+  h->store_vs = sizeof(T);
+  if (h->shard == KRCN_SHARD_NONE) CHK(stored_value_bytes<T>(h, s, &h->store_vs));   // (one scan per build)
   // dense passes: the images must fit the device's free memory (with what the
   // plans about to be replaced give back), checked before anything is
   // allocated or freed so that a refusal leaves the handle as it was
   {
     const bool dn[2] = {pass_format(h, 1) == KRCN_FORMAT_DENSE, pass_format(h, 2) == KRCN_FORMAT_DENSE};
     if ((dn[0] || dn[1]) && h->shard == KRCN_SHARD_NONE) {
-      CHK(dense_value_bytes<T>(h, s, &h->dense_vs));   // (the stored width: the images are sized by it)
-      const int64_t b1 = dn[0] ? dense_geometry(h->n, h->d, h->dense_vs, h->lanes_x, h->slicing).bytes : 0;
-      const int64_t b2 = dn[1] ? dense_geometry(h->d, h->n, h->dense_vs, h->lanes_xt, h->slicing).bytes : 0;
+      const int64_t b1 = dn[0] ? dense_geometry(h->n, h->d, h->store_vs, h->lanes_x, h->slicing).bytes : 0;
+      const int64_t b2 = dn[1] ? dense_geometry(h->d, h->n, h->store_vs, h->lanes_xt, h->slicing).bytes : 0;
       const int64_t need = b1 > INT64_MAX - b2 ? INT64_MAX : b1 + b2;
       size_t mfree = 0, mtotal = 0;
       HIPCHK(hipMemGetInfo(&mfree, &mtotal));
@@ -1226,9 +1265,24 @@ static krcn_status build_plans(krcn_csr* h, bool lz2, hipStream_t s) {
       free_plan(h->p2);
     }
   }
-  CHK(build_plan<T>(h, 2, int(h->d), h->n, h->nnz, h->tptr, h->tidx, static_cast<const T*>(h->tval), h->lanes_xt, s));
+  // One matrix per operator: a window or jagged pass narrows only beside a
+  // pass that narrows too (dense, window or jagged), so no plan pair computes
+  // A32^T diag(w) A.  Pass 2 is built first at the build's stored width; pass
+  // 1 takes that width when pass 2 came out a narrowing kind, and pass 2 is
+  // rebuilt at full width when pass 1 did not (an AUTO plan like rcv1's:
+  // sorted pass 1, jagged pass 2).  The formats' choices do not depend on the
+  // width, so the rebuilt plan has the same kind and geometry.  (A dense image
+  // narrows whatever its partner is: the dense + wave mix keeps that.)
+  auto pass2 = [&](size_t vs) {
+    return build_plan<T>(h, 2, int(h->d), h->n, h->nnz, h->tptr, h->tidx, static_cast<const T*>(h->tval), h->lanes_xt,
+                         vs, s);
+  };
+  CHK(pass2(h->store_vs));
   h->p1_unsliced = lz2 && h->p2.kind == KRCN_PLAN_JAG && h->p2.S == 1 && h->shard == KRCN_SHARD_NONE;
-  return build_plan<T>(h, 1, int(h->n), h->d, h->nnz, h->ptr, h->idx, static_cast<const T*>(h->val), h->lanes_x, s);
+  CHK(build_plan<T>(h, 1, int(h->n), h->d, h->nnz, h->ptr, h->idx, static_cast<const T*>(h->val), h->lanes_x,
+                    plan_narrows(h->p2.kind) ? h->store_vs : sizeof(T), s));
+  if (h->p2.vbytes != int(sizeof(T)) && h->p2.kind != KRCN_PLAN_DENSE && !plan_narrows(h->p1.kind)) CHK(pass2(sizeof(T)));
+  return KRCN_OK;
 }
 
 krcn_status ensure_plans(krcn_csr* h) {

@@ -875,15 +875,16 @@ __global__ __launch_bounds__(kNT) void k_rows_apply(int rows, const T* __restric
       atomicAdd(&counts[int64_t(sid[p]) * rows + r + 1], 1);
 }
 
-template <typename T>
+// (TS: the stored type of the sliced values; T unless a window plan narrows them)
+template <typename T, typename TS>
 __global__ __launch_bounds__(kNT) void k_slice_gather(int64_t nnz, const int* __restrict__ perm,
                                                       const int* __restrict__ idx,
                                                       const T* __restrict__ val,
-                                                      int* __restrict__ sidx, T* __restrict__ sval) {
+                                                      int* __restrict__ sidx, TS* __restrict__ sval) {
   for (int64_t p = int64_t(blockIdx.x) * kNT + threadIdx.x; p < nnz; p += int64_t(gridDim.x) * kNT) {
     const int e = perm[p];
     sidx[p] = idx[e];
-    sval[p] = val[e];
+    sval[p] = static_cast<TS>(val[e]);
   }
 }
 

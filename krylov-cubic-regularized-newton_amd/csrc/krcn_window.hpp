@@ -11,9 +11,11 @@
 // Format (built by krcn_api.hip build_window):
 //  * S slices of W columns; slice s holds columns [s W, (s+1) W) as a CSR
 //    block in slice-major order with 16-bit slice-local column offsets and
-//    the values — 10 bytes per nonzero instead of 12 — and compact row
-//    pointers: a 32-bit base per (slice, tile) plus 16-bit row ends relative
-//    to it.
+//    the values — 10 bytes per nonzero instead of 12 (6 when an fp64 handle
+//    stores fp32 values, KRCN_VALUES_F32: the kernels' stored type TS; same
+//    element order, pads and geometry, values widened at the multiply) — and
+//    compact row pointers: a 32-bit base per (slice, tile) plus 16-bit row
+//    ends relative to it.
 //  * Tiles of R consecutive rows (R = 16/32/64, from the mean row length per
 //    slice); lane l of a wave owns row R t + l of tile t and sums its
 //    elements left to right (1 lane per row — these formats are chosen for
@@ -36,7 +38,8 @@
 //
 // Per tile and slice a wave stages up to kWinChunk nonzeros at a time: each
 // lane loads 4 consecutive (offset, value) pairs with one 8-byte and two
-// 16-byte loads (unconditional: indices past the chunk are clamped), gathers
+// 16-byte loads (one 16-byte load of four fp32 values in a narrowed plan;
+// unconditional: indices past the chunk are clamped), gathers
 // x from the LDS window, writes the products to its private LDS slab, and
 // then every lane adds its row's products out of the slab in order; chunk
 // loads run two tiles ahead (a ring of three slots).  No block-wide barrier
@@ -169,9 +172,12 @@ static __device__ unsigned long long krcn_win_dbg[3 * 2048 * kWinDbgSlots];
 #endif
 
 // One staged chunk: lane l holds nonzeros base + 4 l .. + 3 of [c0, hi).
-template <typename T> struct WinChunk {
+// TS is the stored type of the values (T, or float under fp64 arithmetic:
+// KRCN_VALUES_F32); they stay as loaded and are widened at the multiply
+// (win_consume), so a chunk in flight has no use before it is consumed.
+template <typename T, typename TS = T> struct WinChunk {
   u16x4 q;
-  T v[4];
+  TS v[4];
   int c0, base, hi;
 };
 
@@ -180,32 +186,32 @@ template <typename T> struct WinChunk {
 // around a load would make the compiler drain every outstanding load where
 // the value is used, and the pipeline relies on younger chunks staying in
 // flight while an older one is consumed.
-template <typename T>
-__device__ __forceinline__ void win_load(WinChunk<T>& c, int c0, int e1, const unsigned short* __restrict__ widx,
-                                         const T* __restrict__ wval, int lane) {
+template <typename T, typename TS>
+__device__ __forceinline__ void win_load(WinChunk<T, TS>& c, int c0, int e1, const unsigned short* __restrict__ widx,
+                                         const TS* __restrict__ wval, int lane) {
   c.c0 = c0;
   c.base = c0 & ~3;
   c.hi = c.base + kWinChunk < e1 ? c.base + kWinChunk : e1;
   const int e = c.base + 4 * lane;
   c.q = *reinterpret_cast<const u16x4*>(widx + e);
-  Quad<T>::load(wval + e, c.v);
+  Quad<TS>::load(wval + e, c.v);   // 16-byte aligned for either type: e is a multiple of 4 elements
 }
 
 // Gather x from the window, stage the products in the wave's slab, and add
 // this lane's row elements [beg, end) that fall in the chunk, in order.
-template <typename T>
-__device__ __forceinline__ T win_consume(const WinChunk<T>& c, int beg, int end, const T* win, T* slab, int lane,
+template <typename T, typename TS>
+__device__ __forceinline__ T win_consume(const WinChunk<T, TS>& c, int beg, int end, const T* win, T* slab, int lane,
                                          T s, bool coop = false) {
   const int e = c.base + 4 * lane;
   const unsigned short qi[4] = {c.q.x, c.q.y, c.q.z, c.q.w};
 #if defined(KRCN_WIN_ABL_NOSUM)        // ablation (timing only): no slab, no row walk
 #pragma unroll
-  for (int i = 0; i < 4; ++i) s += c.v[i] * win[e + i < c.hi ? qi[i] : 0];
+  for (int i = 0; i < 4; ++i) s += T(c.v[i]) * win[e + i < c.hi ? qi[i] : 0];
   (void)beg; (void)end; (void)slab;
   return s;
 #else
 #pragma unroll
-  for (int i = 0; i < 4; ++i) slab[4 * lane + i] = c.v[i] * win[e + i < c.hi ? qi[i] : 0];
+  for (int i = 0; i < 4; ++i) slab[4 * lane + i] = T(c.v[i]) * win[e + i < c.hi ? qi[i] : 0];
   wave_lds_sync();
   const int pb = beg > c.c0 ? beg : c.c0;
   const int pe = end < c.hi ? end : c.hi;
@@ -567,7 +573,7 @@ __device__ __forceinline__ void fold_drain(const EpiSliceFold<T>& e, WinFold& f,
 // bounds / epilogue operands of tile k + 1 and the chunk of tile k + 2 are in
 // flight, and the scalar bounds of tile k + 3 are loading.  The window (if
 // the segment loads one) is stored into LDS after the first chunks are issued.
-template <typename T, int R, class Epi>
+template <typename T, typename TS, int R, class Epi>
 __device__ __forceinline__ void win_stream(int segno, const WinSeg& sg, const WinArgs& a,
                                            const T (&tmp)[WinGeom<T>::kPer], bool store_win, int rot, T* win,
                                            T* slab, const Epi& epi, int wave, int lane,
@@ -576,7 +582,7 @@ __device__ __forceinline__ void win_stream(int segno, const WinSeg& sg, const Wi
   const int* tb = a.tb + int64_t(sg.slice) * (a.ntiles + 1);
   const unsigned short* ro = a.ro + int64_t(sg.slice) * rows;
   const unsigned short* widx = a.widx;
-  const T* wval = static_cast<const T*>(a.wval);
+  const TS* wval = static_cast<const TS*>(a.wval);
   const int tw = sg.t0 + wave;
   const int nt = sg.t1 - tw > 0 ? (sg.t1 - tw + kWinWaves - 1) / kWinWaves : 0;
   // tiles in batches of kWinBatch: the ring's look-ahead (5 tiles) stays
@@ -601,7 +607,7 @@ __device__ __forceinline__ void win_stream(int segno, const WinSeg& sg, const Wi
     bounds(B0, 0);
     bounds(B1, 1);
     bounds(B2, 2);
-    WinChunk<T> c0, c1, c2;
+    WinChunk<T, TS> c0, c1, c2;
     RowRaw q0, q1, q2;
     typename Epi::Pre p0, p1, p2;
     auto rows_of = [&](const TileB<R>& b, RowRaw& q, typename Epi::Pre& pr) {
@@ -634,14 +640,14 @@ __device__ __forceinline__ void win_stream(int segno, const WinSeg& sg, const Wi
     }
 #endif
     if (segno < 4 && bi == 0) KRCN_WIN_STAMP(2 + 2 * segno);
-    auto finish = [&](const WinChunk<T>& c, const TileB<R>& b, const RowRaw& q, const typename Epi::Pre& pr,
+    auto finish = [&](const WinChunk<T, TS>& c, const TileB<R>& b, const RowRaw& q, const typename Epi::Pre& pr,
                       int k) {
       int bg, en;
       tile_row_bounds<R>(b, q, lane, bg, en);
       const bool coop = KRCN_WIN_COOP && a.S > 1;
       T s = win_consume(c, bg, en, win, slab, lane, T(0), coop);
       for (int cc = c.hi; cc < b.e1;) {          // tiles longer than one chunk
-        WinChunk<T> cx;
+        WinChunk<T, TS> cx;
         win_load(cx, cc, b.e1, widx, wval, lane);
         s = win_consume(cx, bg, en, win, slab, lane, s, coop);
         cc = cx.hi;
@@ -677,7 +683,7 @@ __device__ __forceinline__ void win_stream(int segno, const WinSeg& sg, const Wi
 // Tiles of one segment in accumulate mode: at most kWinTMax tiles per wave,
 // row sums carried in registers across the block's segments (slices), the
 // epilogue after the last one (FLUSH).  Same ring as win_stream, unrolled.
-template <typename T, int R, class Epi, bool FLUSH>
+template <typename T, typename TS, int R, class Epi, bool FLUSH>
 __device__ __forceinline__ void win_accum(int segno, const WinSeg& sg, const WinArgs& a, const T (&tmp)[WinGeom<T>::kPer],
                                           bool store_win, int rot, T* win, T* slab, const Epi& epi, int wave,
                                           int lane, T (&acc)[kWinTMax], typename RedOf<Epi>::type& red,
@@ -688,7 +694,7 @@ __device__ __forceinline__ void win_accum(int segno, const WinSeg& sg, const Win
   const int* tb = a.tb + int64_t(sg.slice) * (a.ntiles + 1);
   const unsigned short* ro = a.ro + int64_t(sg.slice) * rows;
   const unsigned short* widx = a.widx;
-  const T* wval = static_cast<const T*>(a.wval);
+  const TS* wval = static_cast<const TS*>(a.wval);
   const int nt = sg.t1 - sg.t0 - wave > 0 ? (sg.t1 - sg.t0 - wave + kWinWaves - 1) / kWinWaves : 0;
   (void)tb;
   TileB<R> B[K];   // K <= 64: the whole segment from the batch (kb = 0)
@@ -696,7 +702,7 @@ __device__ __forceinline__ void win_accum(int segno, const WinSeg& sg, const Win
   for (int k = 0; k < K; ++k)
     B[k].set(rows, sg.t0 + wave + k * kWinWaves, sg.t1, __builtin_amdgcn_readlane(tl.e0, k),
              __builtin_amdgcn_readlane(tl.e1, k));
-  WinChunk<T> ring[D];
+  WinChunk<T, TS> ring[D];
   RowRaw rq[D];
   typename Epi::Pre pre[D];
   auto issue_chunk = [&](auto kc) {
@@ -735,12 +741,12 @@ __device__ __forceinline__ void win_accum(int segno, const WinSeg& sg, const Win
     constexpr int k = decltype(kc)::value;
     if constexpr (k + 1 < K) issue_rows(std::integral_constant<int, k + 1>{});
     if constexpr (k + D - 1 < K && D > 1) issue_chunk(std::integral_constant<int, k + D - 1>{});
-    const WinChunk<T>& cur = ring[k % D];
+    const WinChunk<T, TS>& cur = ring[k % D];
     int bg, en;
     tile_row_bounds<R>(B[k], rq[k % D], lane, bg, en);
     T s = win_consume(cur, bg, en, win, slab, lane, acc[k]);
     for (int c = cur.hi; c < B[k].e1;) {
-      WinChunk<T> cx;
+      WinChunk<T, TS> cx;
       win_load(cx, c, B[k].e1, widx, wval, lane);
       s = win_consume(cx, bg, en, win, slab, lane, s);
       c = cx.hi;
@@ -839,7 +845,9 @@ template <typename T> struct IsEpiXt<EpiLz1X<T>> : std::true_type {};
 // The window pass.  Block b runs its segments segs[b * stride + i]; the first
 // segment and its window loads are issued before the source prologue (whose
 // reductions / state reads then overlap them).
-template <typename T, int R, class Src, class Epi, bool kAccum>
+// TS: the stored type of the plan's values (see WinChunk); the window, the
+// slabs, the sums and the epilogue are T's whatever TS is.
+template <typename T, typename TS, int R, class Src, class Epi, bool kAccum>
 __global__ __launch_bounds__(kWinNT, 1) void k_window_pass(WinArgs a, Src src, Epi epi,
                                                            double* __restrict__ partials) {
   constexpr int kPer = WinGeom<T>::kPer;
@@ -985,11 +993,11 @@ __global__ __launch_bounds__(kWinNT, 1) void k_window_pass(WinArgs a, Src src, E
     }
     if constexpr (kAccum) {
       if (sg.flags & kSegFlush)
-        win_accum<T, R, Epi, true>(si, sg, a, tmp, store_win, rot, win, slab, epi, wave, lane, acc, red, tl);
+        win_accum<T, TS, R, Epi, true>(si, sg, a, tmp, store_win, rot, win, slab, epi, wave, lane, acc, red, tl);
       else
-        win_accum<T, R, Epi, false>(si, sg, a, tmp, store_win, rot, win, slab, epi, wave, lane, acc, red, tl);
+        win_accum<T, TS, R, Epi, false>(si, sg, a, tmp, store_win, rot, win, slab, epi, wave, lane, acc, red, tl);
     } else {
-      win_stream<T, R, Epi>(si, sg, a, tmp, store_win, rot, win, slab, epi, wave, lane, red, tl);
+      win_stream<T, TS, R, Epi>(si, sg, a, tmp, store_win, rot, win, slab, epi, wave, lane, red, tl);
     }
     if (si < 4) KRCN_WIN_STAMP(3 + 2 * si);
   }

@@ -121,9 +121,11 @@ class DeviceCSR:
     _VALUES = {"full": _lib.KRCN_VALUES_FULL, "f32": _lib.KRCN_VALUES_F32, "f32-exact": _lib.KRCN_VALUES_F32_EXACT}
 
     def set_value_storage(self, values=0):
-        """Stored width of the dense images' values: "full" / 0 the handle's dtype, "f32" / 1 fp32 (each
+        """Stored width of the plans' matrix values: "full" / 0 the handle's dtype, "f32" / 1 fp32 (each
         value rounded; arithmetic, vectors and sums keep the dtype), "f32-exact" / 2 fp32 only if no
-        value of the matrix changes by it.  CSR-format passes keep full width."""
+        value of the matrix changes by it.  Dense, window and jagged passes honour it (a window or
+        jagged pass only when the other pass narrows too, so both passes see one matrix); wave and
+        sorted passes keep full width.  plan_value_bytes() reports what each pass stores."""
         if isinstance(values, str):
             if values not in self._VALUES:
                 raise ValueError(f'values must be "full", "f32" or "f32-exact", got {values!r}')

@@ -119,13 +119,18 @@ class LogisticRegression(Oracle):
     device / dtype: where and in which precision the device copy of A lives
     (fp64 by default, as the reference computes).  shard: optional
     krcn.dist.ShardSpec for multi-GPU runs (krcn.dist.shard_problem builds it).
-    format: None keeps the handle's format policy, "dense" stores A and A^T as
-    row-major images without indices (nearly dense A such as gisette, madelon
-    or duke; unsharded only), an int is a KRCN_FORMAT_* value.
-    values: with format="dense" only, "f32" stores the images' values in fp32
-    (each rounded; vectors, sums and the recurrence keep the dtype, the matrix
-    bytes of an fp64 pass halve) and "f32-exact" does so only if no value of A
-    changes by it; None or "full" keeps the dtype.
+    format: None keeps the handle's format policy, "auto" names that policy
+    explicitly (KRCN_FORMAT_AUTO), "dense" stores A and A^T as row-major images
+    without indices (nearly dense A such as gisette, madelon or duke; unsharded
+    only), an int is a KRCN_FORMAT_* value.
+    values: "f32" stores the plans' matrix values in fp32 (each rounded;
+    vectors, sums and the recurrence keep the dtype: the objective is then that
+    of double(float(A))) and "f32-exact" does so only if no value of A changes
+    by it; None or "full" keeps the dtype.  Dense, window and jagged plans
+    honour it, so it needs a format named by the caller that can take such a
+    plan: "dense", "auto", KRCN_FORMAT_WINDOW or KRCN_FORMAT_JAG (under "auto" a
+    plan with a wave or sorted pass stays full width: plan_value_bytes()).
+    format=None, wave and sorted raise ValueError.
     """
 
     def __init__(self, A, b, store_mat_vec_prod=False, *args, device=None, dtype=torch.float64,
@@ -135,12 +140,16 @@ class LogisticRegression(Oracle):
             fmt = None if format is None else int(format)
         elif format == "dense":
             fmt = _lib.KRCN_FORMAT_DENSE
+        elif format == "auto":
+            fmt = _lib.KRCN_FORMAT_AUTO
         else:
-            raise ValueError(f"format must be None, 'dense' or a KRCN_FORMAT_* int, got {format!r}")
+            raise ValueError(f"format must be None, 'auto', 'dense' or a KRCN_FORMAT_* int, got {format!r}")
         if values not in (None, "full", "f32", "f32-exact"):
             raise ValueError(f"values must be None, 'full', 'f32' or 'f32-exact', got {values!r}")
-        if values not in (None, "full") and fmt != _lib.KRCN_FORMAT_DENSE:
-            raise ValueError(f"values={values!r} needs format='dense': only dense passes store narrowed values")
+        narrowing = (_lib.KRCN_FORMAT_AUTO, _lib.KRCN_FORMAT_WINDOW, _lib.KRCN_FORMAT_JAG, _lib.KRCN_FORMAT_DENSE)
+        if values not in (None, "full") and fmt not in narrowing:
+            raise ValueError(f"values={values!r} needs format='dense', 'auto', KRCN_FORMAT_WINDOW or KRCN_FORMAT_JAG: "
+                             "only dense, window and jagged passes store narrowed values")
         import scipy.sparse as sp
         self.A = A
         self.b = _labels01(b)
