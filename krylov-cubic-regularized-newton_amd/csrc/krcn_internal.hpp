@@ -2,13 +2,20 @@
 //
 // The library is split into translation units that compile in parallel:
 //   krcn_handle.hip      error recorder, handle lifecycle, transposed CSR, setters / getters, profiling
-//   krcn_plan.hip        the pass-plan builders, ensure_plans, the reorth workspace
+//   krcn_plan.hip        the pass plans on the device (layouts: krcn_layout.hpp), ensure_plans, the reorth workspace
 //   krcn_place.hip       the placement probe and the placement search over Lanczos calls
 //   krcn_comm.hip        the RCCL communicator and the virtual communicator
 //   krcn_ops.hip         objective pieces (Ax, X^T u, weights, HVP, gradient, loss, dots)
 //   krcn_coord.hip       coordinate blocks of SSCN (gradient, Hessian block, Ax update)
 //   krcn_lanczos_f64.hip / krcn_lanczos_f32.hip
 //                        the device Lanczos recurrence (krcn_lanczos_impl.hpp), one dtype each
+// Two host-only headers (plain C++17, no HIP header: they also build with g++
+// under the host sanitizers, tests/native/layout_check.cpp):
+//   krcn_geom.hpp        the constants and small structs host and device agree through (block
+//                        shapes, tile caps, LDS geometry, TileDesc / WinSeg, the lane rule, the
+//                        tuning-knob readers); the kernel headers include it
+//   krcn_layout.hpp      the format policy and one layout function per format, from host row
+//                        pointers to plain structs; krcn_plan.hip materialises them on the device
 // This header holds the handle layout, the error macros and the host helpers;
 // it ends by including
 //   krcn_pass.hpp        the pass launcher (run_pass, run_combine, the shape of a pass) that the
@@ -41,37 +48,6 @@
 #include <vector>
 
 using namespace krcn;
-
-// A/B tuning knobs (the variants of DESIGN.md's measurements) are read from
-// the environment only in tuning builds (make variant EXTRA_FLAGS=-DKRCN_TUNING);
-// the product library runs the measured defaults whatever the environment holds.
-inline const char* tuning_env(const char* name) {
-#ifdef KRCN_TUNING
-  return getenv(name);
-#else
-  (void)name;
-  return nullptr;
-#endif
-}
-// The three readings of a knob: a number (dflt when unset; V is int, int64_t
-// or double; field f of a comma-separated list), a switch that is on unless
-// set to 0, one that is off unless set to 1.  A site keeps the value in a
-// function-local static and checks its range.
-template <typename V>
-inline V tuning_value(const char* name, V dflt, int field = 0) {
-  const char* e = tuning_env(name);
-  for (; e && field > 0; --field)
-    if ((e = std::strchr(e, ',')) != nullptr) ++e;
-  return e ? V(std::atof(e)) : dflt;
-}
-inline bool tuning_on(const char* name) {
-  const char* e = tuning_env(name);
-  return !(e && e[0] == '0');
-}
-inline bool tuning_off(const char* name) {
-  const char* e = tuning_env(name);
-  return e && e[0] == '1';
-}
 
 // CGS2 colsweep shape (krcn_cgs2.hpp k_cgs_colsweep): rows per wave and batch
 // past k = 4 U (tuning knob KRCN_CGS_COLU) and batches per block (KRCN_CGS_NB);
@@ -385,8 +361,6 @@ struct krcn_csr {
   hipEvent_t lzp_e0 = nullptr, lzp_e1 = nullptr;
 };
 
-constexpr int kNumCUs = 256;   // MI355X: 8 XCDs x 32 CUs
-
 void free_plan(PassPlan& P);
 void coord_free(krcn_csr* h);   // krcn_coord.hip: releases h->cw
 krcn_status ensure_plans(krcn_csr* h);
@@ -432,21 +406,6 @@ inline int vec_grid(int64_t len) {
   if (b < 1) b = 1;
   if (b > 1024) b = 1024;
   return int(b);
-}
-
-// Lanes per row: the largest power of two <= mean row length / 8, in [1, 64]
-// (measured on news20 / rcv1 shapes: 6.7 nnz/row -> 1, 57 -> 4, 74 -> 8).
-inline int auto_lanes(int64_t rows, int64_t nnz) {
-  const double mean = rows > 0 ? double(nnz) / double(rows) : 0.0;
-  int L = 1;
-  while (L < 64 && double(L * 2) * 8.0 <= mean) L *= 2;
-  return L;
-}
-
-inline int resolve_lanes(int policy, int64_t rows, int64_t nnz) {
-  if (policy == KRCN_LANES_AUTO) return auto_lanes(rows, nnz);
-  if (policy == KRCN_LANES_SEQUENTIAL) return 1;
-  return policy;
 }
 
 inline krcn_status set_device(const krcn_csr* h) {

@@ -61,50 +61,7 @@ namespace krcn {
 #ifndef KRCN_JAG_EARLY
 #define KRCN_JAG_EARLY 1   // single-window pass: the first chunk goes out with the window fetch
 #endif
-constexpr int kJagNT = 1024;                     // one block per CU: the window takes the LDS
-constexpr int kJagWaves = kJagNT / 64;
-constexpr int kJagLdsBytes = 163840 - 256;       // window(s); 256 B stay for the block reduction
-constexpr int kJagPieces = kJagLdsBytes / 16;    // 16-byte pieces of window: 10,224
-constexpr int kJagSlab = 128;                    // accumulate mode: elements per unit (products slab)
-constexpr int kJagPad = 2 * kJagSlab;            // element arrays' padding (unit loads past the end)
-
-// Variants (host and device agree through these):
-//   single window (k_jag_pass): K <= 6 groups per wave, 2 chunks of 8 levels,
-//                               8-bit counts
-//   accumulate (k_jag_acc):     K = 4 or 8 groups per wave, <= 128 elements
-//                               per unit, 8-bit counts
-#ifndef KRCN_JAG_CPG
-#define KRCN_JAG_CPG 2   // static chunks per unit of K >= 3 plans (A/B: variant builds)
-#endif
-constexpr int kJagK1 = 6, kJagCPG1 = KRCN_JAG_CPG, kJagLC = 8;
-// the first kJagCPGU chunks of a unit are loaded whatever its counts; later
-// static chunks only when some lane of the wave has levels there (a wave-
-// uniform test).  Measured (round 6, -DKRCN_JAG_CPG=3): news20's X^T rows
-// (Poisson, mean 6.7) pass 16 levels in 3.9 % of the 64-row groups, so most
-// blocks wait for one synchronous overflow round trip — but a third static
-// chunk makes the fused Lanczos pass 2 spill 44 B and run 27.9 -> 38.9 us
-// (profiles/r06ag_news20_cpg3_ab.txt); the default stays 2
-constexpr int kJagCPGU = 2;
-// K <= 2 plans (rcv1's X^T: rows to 60 levels) keep 2 static chunks and run
-// the overflow one chunk ahead instead (a third static chunk would spill)
-constexpr int jag_cpg(int K) { return K <= 2 ? 2 : kJagCPG1; }
-constexpr int kJagK2 = 8;                        // largest accumulate K (4 when the groups allow)
-// Single window, long rows: rows with more than kJagLong elements leave the
-// lane-per-row units (a 64-row group would wait for its longest row) and are
-// summed by whole waves in tasks of kJagTask elements, <= kJagLongTasks tasks a
-// block (their partials sit in LDS past the window).
-constexpr int kJagLong = 32, kJagTask = 128, kJagLongTasks = 256;
-
-template <typename T> struct JagGeom {
-  static constexpr int kE = 16 / int(sizeof(T));                       // entries per piece
-  static constexpr int kW1 = kJagPieces * kE;                          // single window (fp64 20,448)
-  static constexpr int kR1 = (kJagPieces + kJagNT - 1) / kJagNT;       // piece loads per thread
-  // accumulate: two windows beside the 16 per-wave product slabs
-  static constexpr int kPieces2 = (kJagLdsBytes - kJagWaves * (kJagSlab + 2) * int(sizeof(T))) / 32;
-  static constexpr int kW2 = kPieces2 * kE;                            // fp64 9,200; fp32 19,424
-  static constexpr int kR2 = (kPieces2 + kJagNT - 1) / kJagNT;
-  static_assert(kW1 <= 65536, "16-bit slice-local offsets");
-};
+// (the kJag* constants, jag_cpg and JagGeom: krcn_geom.hpp)
 
 struct JagArgs {
   int rows, S, W, G;                  // accumulate: S slices per group, G slice groups (block b: group b % G)

@@ -19,9 +19,10 @@
 
 #include <type_traits>
 
+#include "krcn_geom.hpp"
+
 namespace krcn {
 
-constexpr int kNT = 256;           // threads per block for every kernel here
 constexpr int kUnroll = 4;         // elementwise kernels: independent loads per array per thread
 
 constexpr int kMaxPartials = 2048;  // upper bound on blocks of a reducing launch

@@ -29,13 +29,6 @@
 
 namespace krcn {
 
-// One tile: rows [row0, row1) of slice `slice`, nonzeros [p0, p1) of the
-// pass's CSR arrays; long_row != 0 marks a single row with more than
-// kWaveTileNnz nonzeros.  32 bytes: one scalar load per tile.
-struct __attribute__((aligned(32))) TileDesc {
-  int slice, long_row, row0, row1, p0, p1, pad0, pad1;
-};
-
 // Source of the gathered vector x for a pass: begin(sm) runs once per block
 // (it may reduce partials and return true to skip the launch), get() the vector.
 // early(): the vector get() will return, known before begin() runs (a
@@ -352,10 +345,7 @@ template <typename T> struct EpiSlicePart {
 // loads (int4 / double2 / float4), issues every gather of x before it touches
 // LDS, stores the products in its private LDS slab, stages the tile's row
 // pointers next to them, and reduces its rows out of LDS.
-constexpr int kWaveTileNnz = 512;                    // nonzeros per wave tile
-constexpr int kWaveTileRows = 128;                   // rows per wave tile (cap)
 constexpr int kProdSlots = kWaveTileNnz + 8;         // 4-aligned window (+ pad)
-constexpr int kWavesPerBlock = kNT / 64;
 #ifndef KRCN_TILE_WAVES
 #define KRCN_TILE_WAVES 1
 #endif
@@ -542,22 +532,9 @@ __global__ __launch_bounds__(kNT, KRCN_TILE_WAVES) void k_tiled_pass(int rows, i
 // row i left to right (all its loads issued before the first add), then a
 // fixed tree over the 8 phases.  Deterministic; the order does not depend on
 // the grid.
-constexpr int kCombineRows = 128;
 constexpr int kCombineNT = 1024;
 constexpr int kCombinePh = kCombineNT / kCombineRows;
 constexpr int kCombineU = 16;   // loads in flight per thread
-constexpr int kCombineSpread = 256;   // one row range per CU (MI355X: 256 CUs)
-__host__ inline int combine_rows(int rows) {
-  const int R = (rows + kCombineSpread - 1) / kCombineSpread;
-  return R < 1 ? 1 : (R > kCombineRows ? kCombineRows : R);
-}
-// at most one block per CU: past 256 x 128 rows a block walks several ranges
-// (each block runs the source prologue, e.g. the beta reduction, once)
-__host__ inline int combine_grid(int rows) {
-  const int R = combine_rows(rows);
-  const int g = (rows + R - 1) / R;
-  return g < 1 ? 1 : (g > kCombineSpread ? kCombineSpread : g);
-}
 template <typename T, class Src, class Epi>
 __global__ __launch_bounds__(kCombineNT) void k_slice_combine(int rows, int S, int R, const T* __restrict__ part,
                                                               Src src, Epi epi, double* __restrict__ partials) {
@@ -912,23 +889,12 @@ namespace krcn {
 #endif
 __device__ __forceinline__ int lds_sw(int p) { return KRCN_SORT_SWIZZLE ? p ^ ((p >> 4) & 15) : p; }
 
-constexpr int kSortPerThread = 8;
-constexpr int ilog2(int v) { return v <= 1 ? 0 : 1 + ilog2(v / 2); }
 // Occupancy the sorted pass is built for: 8 waves per SIMD (2 blocks of 1024, 4 blocks
 // of 512 or 8 of 256 threads per CU, matching the LDS footprint), so the
 // register allocator keeps to 64 VGPRs.
 #ifndef KRCN_SORT_WAVES
 #define KRCN_SORT_WAVES 8
 #endif
-template <int NT> struct SortGeom {
-  static constexpr int kTile = NT * kSortPerThread;   // nonzeros per block tile / sort segment
-  static constexpr int kRows = kTile / 4;             // rows per block tile (cap)
-  static constexpr int kRowRegs = (kRows + 1 + NT - 1) / NT;   // row pointers per thread
-  static constexpr int kSlotBits = ilog2(kTile);
-  static_assert((1 << kSlotBits) == kTile, "slot field must address a whole tile");
-  // packed word: (column - tile's column base) << kSlotBits | slot
-  static constexpr int64_t kMaxWindow = int64_t(1) << (32 - kSlotBits);
-};
 
 // Per-thread staging of one sorted tile.  Every load is unconditional (index
 // clamped into the tile, result selected): a branch around a load makes the

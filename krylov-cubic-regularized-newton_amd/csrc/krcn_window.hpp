@@ -52,18 +52,7 @@
 
 namespace krcn {
 
-struct __attribute__((aligned(16))) WinSeg {
-  int slice, t0, t1, flags;   // flags: kSegLoad | kSegFlush | (segments of the block << 8, first entry only)
-};
-enum { kSegLoad = 1, kSegFlush = 2 };
-
-constexpr int kWinNT = 1024;                 // one block per CU (the window takes the LDS)
-constexpr int kWinWaves = kWinNT / 64;
-constexpr int kWinChunk = 256;               // nonzeros per staging step (4 per lane)
-constexpr int kWinTMax = 6;                  // accumulate mode: tiles per wave (register sums)
-constexpr int kWinPad = kWinChunk + 8;       // array padding: unconditional chunk loads stay in bounds
-constexpr int kWinRing = 3;                  // chunk slots in flight per wave (slices mode)
-constexpr int kWinBatch = 58;                // slices mode: tiles per batch of tile bases (64 - the look-ahead)
+// (WinSeg, the kWin* constants, WinGeom and win_block_slice: krcn_geom.hpp)
 #ifndef KRCN_WIN_RING_ACCUM
 #define KRCN_WIN_RING_ACCUM 2
 #endif
@@ -78,14 +67,6 @@ constexpr int kWinCoopLen = 64;              // (KRCN_WIN_COOP) run length past 
 #ifndef KRCN_WIN_FIRST
 #define KRCN_WIN_FIRST 1   // window stored before the first chunk loads go out
 #endif
-// LDS: window + 16 slabs of kWinChunk + the reduction scratch must fit 160 KiB
-template <typename T> struct WinGeom {
-  static constexpr int kSlabBytes = kWinWaves * kWinChunk * int(sizeof(T));
-  static constexpr int kBytes = 163840 - kSlabBytes - 256;
-  static constexpr int kW = kBytes / int(sizeof(T));      // max window (fp64 16,352; fp32 32,704)
-  static constexpr int kPer = (kW + kWinNT - 1) / kWinNT;  // window entries per thread
-  static_assert(kW <= 65536, "16-bit slice-local offsets");
-};
 
 struct WinArgs {
   int rows, W, stride, S;
@@ -99,24 +80,6 @@ struct WinArgs {
   const WinSeg* segs;            // block b: segs[b * stride + i]
   int kpb = 0;                   // slices mode: win_block_slice's mapping (0: block = slice + S chunk)
 };
-
-// Slices mode: block b's slice and row chunk.  kpb == 0: b = slice + S chunk
-// (S a multiple of 8 and kpb a power of two: the slice's blocks share an XCD,
-// b % 8).  Else (round 5: 85 slices x 3 blocks) the blocks of XCD b % 8 take
-// consecutive slots of a slice-major numbering (slot = kpb slice + chunk):
-// slot = (slots of the XCDs before b's) + b / 8, so a slice's blocks share
-// an XCD except where its slots straddle two XCDs.  G = the grid.
-__host__ __device__ inline void win_block_slice(int b, int G, int S, int kpb, int& slice, int& chunk) {
-  if (kpb == 0) {
-    slice = b % S;
-    chunk = b / S;
-    return;
-  }
-  const int x = b % 8, q = G / 8, r = G % 8;
-  const int slot = x * q + (x < r ? x : r) + b / 8;
-  slice = slot / kpb;
-  chunk = slot % kpb;
-}
 
 typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
 
@@ -771,12 +734,7 @@ __device__ __forceinline__ void win_accum(int segno, const WinSeg& sg, const Win
 // the column's chunk range load together) and no serial walk down a long
 // column.  k_xt_combine then adds the blocks in a fixed order and runs step A
 // (EpiLz2): pass 2 never re-reads the matrix and has no launch of its own.
-constexpr int kXtChunk = 4;
-constexpr int kXtRowCap = kWinWaves * kWinTMax * 64;   // rows of one accumulate block (<= 96 tiles of <= 64)
-constexpr unsigned short kXtPad = 0xFFFF;
-template <typename T> struct XtGeom {
-  static constexpr int kChunks = WinGeom<T>::kW - kWinNT - kXtRowCap;   // chunk sums in LDS past lu
-};
+// (kXtChunk, kXtRowCap, kXtPad and XtGeom: krcn_geom.hpp)
 template <typename T> struct EpiLz1X {
   const T* w; T div;
   const int* xcp;               // per block: cols + 1 absolute chunk ids (column c: [xcp[c], xcp[c+1]))

@@ -10,7 +10,11 @@ build, with g++ and AddressSanitizer + UBSan or ThreadSanitizer:
     passes another count);
   * svm_cli_{asan,tsan}: the multithreaded svmlight parser (csrc/
     krcn_svmlight.hip) behind a command line; the inputs of
-    tests/test_libsvm.py go through it and must equal sklearn's parse.
+    tests/test_libsvm.py go through it and must equal sklearn's parse;
+  * layout_asan: the pass-plan layouts (csrc/krcn_layout.hpp) behind
+    tests/native/layout_check.cpp, which checks every layout's invariants on
+    small patterns at the boundaries of the layout rules (ASan + UBSan only:
+    the layouts are single-threaded).
 A sanitizer finding aborts the program (-fno-sanitize-recover), so every
 check here is also "no report".
 """
@@ -115,3 +119,124 @@ def test_svm_multithreaded_large_file(san, tmp_path):
     assert path.stat().st_size > (2 << 20)
     for t in (1, 8, 13):
         _same_as_sklearn(san, path, t, tmp_path)
+
+
+# ---------------------------------------------------------------- plan layouts
+# layout_asan (tests/native/layout_check.cpp): the host-only pass-plan layouts
+# of csrc/krcn_layout.hpp on small patterns at the boundaries of their rules.
+# The program checks every layout invariant itself (cuts, caps, partitions,
+# flags, task tables) and exits non-zero on a violation or a sanitizer report;
+# the tests add what the boundary should decide.
+from test_plan_layouts import run_layout, write_pattern   # noqa: E402
+
+LAYOUT = os.path.join(NATIVE, "layout_asan")
+WAVE, SORTED, WINDOW, JAG = 1, 2, 3, 4
+KW = {"f64": 16352, "f32": 36800}        # WinGeom<T>::kW = (163,840 - 16 slabs of 256 values - 256) / sizeof(T)
+KW1 = {"f64": 20448, "f32": 40896}       # JagGeom<T>::kW1 (one window)
+KW2 = {"f64": 9200, "f32": 19424}        # JagGeom<T>::kW2 (two windows beside the product slabs)
+
+
+def _pattern(tmp_path, lengths, cols, seed=0, name="p.bin"):
+    """Rows of the given lengths over `cols` columns (sorted, unique), as layout_check reads them."""
+    rng = np.random.default_rng(seed)
+    lengths = np.asarray(lengths, dtype=np.int64)
+    idx = [np.sort(rng.choice(cols, size=int(n), replace=False)) for n in lengths if n]
+    path = tmp_path / name
+    write_pattern(path, np.concatenate([[0], np.cumsum(lengths)]), np.concatenate(idx) if idx else [], cols)
+    return path
+
+
+@pytest.mark.parametrize("dt", ["f64", "f32"])
+@pytest.mark.parametrize("rows", [0, 1, 63, 64, 65, 129])
+def test_layout_row_counts(rows, dt, tmp_path):
+    """Every format around the 64-row group / tile edge; no rows at all: the jagged format refuses."""
+    p = _pattern(tmp_path, [3] * rows, 500)
+    for fmt in (WAVE, SORTED, WINDOW, JAG):
+        for pass_ in (1, 2):
+            got = run_layout(LAYOUT, p, fmt, dt, pass_, expect_refusal=fmt == JAG and rows == 0)
+            if fmt == JAG and rows == 0:
+                assert "empty or too narrow" in got["refused"]
+            elif fmt == JAG:
+                assert got["ntiles"] == (rows + 63) // 64 and got["grid"] >= 1
+            else:
+                assert got["grid"] >= 1
+
+
+@pytest.mark.parametrize("dt", ["f64", "f32"])
+def test_layout_empty_rows_and_no_nonzeros(dt, tmp_path):
+    """Empty rows at the start, in the middle and at the end; a matrix without nonzeros."""
+    lengths = [0] * 70 + [5, 9, 2] * 30 + [0] * 130 + [7] * 40 + [0] * 66
+    p = _pattern(tmp_path, lengths, 3000)
+    z = _pattern(tmp_path, [0] * 100, 3000, name="z.bin")
+    for fmt in (WAVE, SORTED, WINDOW, JAG):
+        for slicing in ((0, 8) if fmt in (WAVE, SORTED) else (0,)):
+            run_layout(LAYOUT, p, fmt, dt, 1, slicing=slicing)
+            got = run_layout(LAYOUT, z, fmt, dt, 1, slicing=slicing, expect_refusal=fmt == JAG)
+            assert ("refused" in got) == (fmt == JAG)
+
+
+def test_layout_jag_long_row_thresholds(tmp_path):
+    """kJagLong: a row of 32 elements stays in the lane-per-row units, one of 33 goes long.  With a
+    window that leaves fewer than 256 task partials (20,400 fp64 entries: 48), rows go long only once
+    some row passes the 254 elements an 8-bit lane count holds."""
+    for n, nlong in ((32, 0), (33, 1)):
+        got = run_layout(LAYOUT, _pattern(tmp_path, [4] * 100 + [n] + [4] * 100, 500), JAG, "f64", 1)
+        assert (got["S"], got["lthr"], got["nlong"]) == (1, 32, nlong)
+    for n, lthr, nlong in ((254, 0, 0), (255, 32, 2)):
+        got = run_layout(LAYOUT, _pattern(tmp_path, [4] * 100 + [n, 40] + [4] * 100, 20_400), JAG, "f64", 1)
+        assert (got["S"], got["tcap"], got["lthr"], got["nlong"]) == (1, 48, lthr, nlong)
+    # the sequential lane policy keeps every row lane-per-row
+    got = run_layout(LAYOUT, _pattern(tmp_path, [4] * 100 + [33] + [4] * 100, 500), JAG, "f64", 1, seq=1)
+    assert got["nlong"] == 0
+
+
+def test_layout_jag_task_cap(tmp_path):
+    """One block (64 rows) whose long row needs tcap - 1, tcap and tcap + 1 tasks of 128 elements
+    (tcap = 48 beside a 20,400-entry fp64 window): the last is refused."""
+    for tasks in (47, 48):
+        got = run_layout(LAYOUT, _pattern(tmp_path, [4] * 30 + [128 * tasks] + [4] * 33, 20_400), JAG, "f64", 1)
+        assert (got["grid"], got["tcap"], got["nlong"], got["maxtasks"]) == (1, 48, 1, tasks)
+    got = run_layout(LAYOUT, _pattern(tmp_path, [4] * 30 + [128 * 49] + [4] * 33, 20_400), JAG, "f64", 1,
+                     expect_refusal=True)
+    assert "long rows need 49 tasks (max 48)" in got["refused"]
+
+
+@pytest.mark.parametrize("dt", ["f64", "f32"])
+def test_layout_window_and_jag_slice_edges(dt, tmp_path):
+    """One more column than a window holds: the jagged format leaves its single window at kW1 for
+    ceil(cols / kW2) = 3 double-buffered slices; the forced window format goes from 4 accumulate slices
+    to window slices at 4 kW."""
+    lengths = [3] * 200
+    assert run_layout(LAYOUT, _pattern(tmp_path, lengths, KW1[dt]), JAG, dt, 1)["S"] == 1
+    assert run_layout(LAYOUT, _pattern(tmp_path, lengths, KW1[dt] + 1), JAG, dt, 1)["S"] == -(-(KW1[dt] + 1) // KW2[dt]) == 3
+    got = run_layout(LAYOUT, _pattern(tmp_path, lengths, 4 * KW[dt]), WINDOW, dt, 1)
+    assert (got["kind"], got["S"], got["W"]) == (4, 4, KW[dt])
+    got = run_layout(LAYOUT, _pattern(tmp_path, lengths, 4 * KW[dt] + 1), WINDOW, dt, 1)
+    assert (got["kind"], got["S"], got["grid"]) == (3, 8, 256)
+
+
+@pytest.mark.parametrize("dt", ["f64", "f32"])
+def test_layout_xt_copy_edge(dt, tmp_path):
+    """The per-block X^T copy of a one-piece accumulate plan: made up to 1,024 columns, not past them."""
+    lengths = [4] * 300 + [0] * 20 + [900] + [4] * 100
+    assert run_layout(LAYOUT, _pattern(tmp_path, lengths, 1024), WINDOW, dt, 1, accum=1)["xt"] == 1
+    assert run_layout(LAYOUT, _pattern(tmp_path, lengths, 1025), WINDOW, dt, 1, accum=1)["xt"] == 0
+
+
+def test_layout_window_slices_empty_chunks(tmp_path):
+    """Fewer tiles (300 rows: at most 19) than the 32 blocks of each of 8 slices: blocks with an empty
+    row chunk still name their slice."""
+    got = run_layout(LAYOUT, _pattern(tmp_path, [40] * 300, 100_000), WINDOW, "f64", 1)
+    assert (got["kind"], got["S"], got["kpb"], got["grid"]) == (3, 8, 32, 256)
+    assert got["ntiles"] < 32 and got["empty"] >= 8 * (32 - got["ntiles"])
+
+
+def test_layout_skew_lane_rule(tmp_path):
+    """Sorted pass 1, automatic lanes.  Uniform rows of 64: the plain mean's L = 8.  199 rows of 8 and one
+    of 4,000: mean 28 (L = 2), nonzero-weighted mean 2,863 >= 2 x 28, so lanes come from 4 x 2,863: 64.
+    Pass 2 keeps the plain mean."""
+    uni = _pattern(tmp_path, [64] * 200, 5000, name="u.bin")
+    skew = _pattern(tmp_path, [8] * 199 + [4000], 5000, name="s.bin")
+    assert run_layout(LAYOUT, uni, SORTED, "f64", 1)["L"] == 8
+    assert run_layout(LAYOUT, skew, SORTED, "f64", 1)["L"] == 64
+    assert run_layout(LAYOUT, skew, SORTED, "f64", 2)["L"] == 2
