@@ -22,7 +22,9 @@
  *     partials (krcn_csr_reserve, krcn_csr_attach_comm of a multi-rank
  *     communicator, the plan queries, or the first compute call of any other
  *     handle), in krcn_csr_reserve(.., reorth = 1) (CGS2 workspace) and in the
- *     first krcn_cg_solve.  krcn_lanczos allocates nothing on a handle that is
+ *     first krcn_cg_solve, and the workspace of krcn_crn_step / krcn_cubic_tridiag
+ *     (about 50 KB) in krcn_csr_reserve of an unsharded handle or the first of
+ *     those calls.  krcn_lanczos allocates nothing on a handle that is
  *     reserved for its m.  The coordinate calls (krcn_coord_*) allocate their
  *     own workspace at the first of them and grow it when k grows: the device
  *     cols and delta (k_cap int32 + k_cap doubles) and a k_cap x k_cap fp64
@@ -212,6 +214,22 @@ typedef struct {
   int pad;
   double residual_norm;  /* ||r|| after the last update                            */
 } krcn_cg_info;
+
+/* Result record of krcn_crn_step; krcn_cubic_tridiag fills its solver fields
+ * (solver_it, solver_status, reg_coef, lam, model_decrease) and zeroes the rest. */
+typedef struct {
+  int accepted;         /* 1: a trial met value_new <= value - model_decrease           */
+  int trials;           /* backtracking trials after the first solve (0..max_trials)   */
+  int solver_it;        /* Newton iterations of the last subproblem solve              */
+  int solver_status;    /* 0 ok, 1 T + lam I not positive definite, 2 derivative zero,
+                           3 it_max reached (root still returned, as root_scalar does) */
+  double reg_coef;      /* M of the last solve                                         */
+  double lam;           /* its root (the caller's next r0)                             */
+  double model_decrease;
+  double value_new;     /* f(x_new), l2 term included                                  */
+  double dx_norm;       /* ||x_new - x||_2, krcn_diff_norm's bits                      */
+  krcn_lanczos_info lanczos;
+} krcn_crn_info;
 
 /* ---- library ------------------------------------------------------------ */
 const char* krcn_last_error_string(void);
@@ -442,6 +460,49 @@ krcn_status krcn_basis_combine(krcn_csr* h, int m_eff, const void* V,
 krcn_status krcn_cg_solve(krcn_csr* h, const void* w, const void* b, double shift,
                           double rtol, int maxiter, void* x,
                           krcn_cg_info* info_host, void* stream);
+
+/* ---- the Krylov-CRN step on the device ---------------------------------- */
+/* SYNCHRONOUS.  argmin_s <g,s> + 1/2 s^T T s + M/3 ||s||^3 for
+ * T = tridiag(betas, alphas, betas) (m and m - 1 host entries; betas_host may
+ * be NULL when m = 1) and g = gnorm e1, solved by one workgroup on the device
+ * in fp64 whatever the handle's dtype: scipy's scalar Newton (root_scalar,
+ * method="newton", x0 = r0, xtol = eps, maxiter = it_max) on
+ * phi(lam) = lam^2 - M^2 ||s(lam)||^2, each shifted solve an LDL^T of
+ * T + lam I by dpttrf's recurrence with dpttrs's substitutions, and the
+ * reference's closing expressions.  s_host receives the m entries of s (zeros
+ * when the solve failed: solver_status 1 or 2); 1 <= m <= 2044, it_max >= 1.
+ * Allocates the step workspace on a handle that was not reserved.
+ * Replaces cubic_solver_root on the Krylov subspace model, cubic.py:40-75
+ * (called at cubic.py:285-286, :298-299). */
+krcn_status krcn_cubic_tridiag(krcn_csr* h, int m, const double* alphas_host, const double* betas_host,
+                               double gnorm, double M, double r0, double eps, int it_max,
+                               double* s_host, krcn_crn_info* info_host, void* stream);
+
+/* SYNCHRONOUS.  One Krylov-CRN step from x with f(x) = value: Ax = X x if Ax is
+ * NULL, the gradient, the Hessian weights, the m-step Lanczos recurrence of
+ * krcn_lanczos (same reorth / tol / l2; its alphas, betas and state stay on the
+ * device), then the line search: M = reg_coef * ls_beta, trial 0, and while
+ * value_new > value - model_decrease and trials < max_trials: M /= ls_beta and
+ * the next trial.  A trial is the subproblem of krcn_cubic_tridiag from r0
+ * (every trial starts from the caller's r0), x_new = x + V^T s,
+ * Ax_new = X x_new, f(x_new) = mean + l2 / 2 * ||x_new||^2, and the test; the
+ * decision is taken on the device and the launches of later trials are guarded
+ * by it, so x_new / Ax_new hold the accepted trial (the last one at the cap).
+ * The host enqueues trials 0 and 1, then batches of four, and synchronises once
+ * per batch.  A failed solve (solver_status 1 or 2) ends the chain; x_new and
+ * Ax_new are then unspecified.  V is the basis (m rows x d, as krcn_lanczos),
+ * x_new a d-vector and Ax_new an n-vector that alias no input; alphas_host[m]
+ * and betas_host[max(m-1,1)] receive the recurrence's results as krcn_lanczos
+ * returns them and may be NULL.  Graph replay and the Lanczos placement search
+ * do not run inside this call.  Unsharded handles only
+ * (KRCN_ERR_UNSUPPORTED otherwise); allocates nothing on a reserved handle
+ * (krcn_csr_reserve also reserves this call's workspace).
+ * Replaces the body of Cubic_Krylov_LS.step, cubic.py:265-309. */
+krcn_status krcn_crn_step(krcn_csr* h, const void* x, const void* b, const void* Ax, double value,
+                          int m, int reorth, double tol, double l2, double reg_coef, double ls_beta,
+                          double r0, double solver_eps, int solver_it_max, int max_trials, void* V,
+                          void* x_new, void* Ax_new, double* alphas_host, double* betas_host,
+                          krcn_crn_info* info_host, void* stream);
 
 /* ---- dense vector helpers (host glue of optimizer.py / utils.py) -------- */
 /* Vector spaces of a handle: n-vectors (one entry per sample row) and

@@ -7,6 +7,7 @@
 //   krcn_comm.hip        the RCCL communicator and the virtual communicator
 //   krcn_ops.hip         objective pieces (Ax, X^T u, weights, HVP, gradient, loss, dots)
 //   krcn_coord.hip       coordinate blocks of SSCN (gradient, Hessian block, Ax update)
+//   krcn_crn.hip         the device cubic subproblem and the one-call Krylov-CRN step (krcn_cubic.hpp)
 //   krcn_lanczos_f64.hip / krcn_lanczos_f32.hip
 //                        the device Lanczos recurrence (krcn_lanczos_impl.hpp), one dtype each
 // Two host-only headers (plain C++17, no HIP header: they also build with g++
@@ -324,6 +325,10 @@ struct krcn_csr {
   int reorth_m = 0;           // CGS2 workspace reserved for Lanczos m <= this (krcn_csr_reserve)
   void* cg_r = nullptr;       // CG vectors r | p | q (3 d-vectors, krcn_cg_solve)
   struct krcn::CgState* cg_st = nullptr;
+  double* crn_ws = nullptr;   // krcn_crn_step / krcn_cubic_tridiag: the chain state, then the subproblem's
+                              // alphas | betas | s (three kLzMaxM-vectors; its solves work in LDS)
+  double* crn_res = nullptr;  //   pinned, mapped host record the judge kernel writes (krcn_crn.hip)
+  double* crn_res_dev = nullptr;
   CoordWs* cw = nullptr;      // coordinate workspace (first krcn_coord_* call; its device block is in own)
   int coord_window = 0;       // krcn_csr_set_coord_window (0: auto)
   DevOwner own;               // every device buffer above but betas_dev (it aliases alphas_dev)
@@ -454,9 +459,38 @@ inline ProfRec* prof_next(krcn_csr* h) {
 }
 
 // Lanczos recurrences, one translation unit per dtype (krcn_lanczos_impl.hpp).
+// enqueue_only (krcn_crn_step): the launches alone — no graph replay, no
+// placement search, no synchronisation; the host arrays and info are left
+// untouched and the caller reads them with lanczos_results after its own sync.
 krcn_status lanczos_f64(krcn_csr* h, const double* w, const double* g, int m, int reorth, double tol, double l2,
-                        double* V, double* alphas_host, double* betas_host, krcn_lanczos_info* info, hipStream_t s);
+                        double* V, double* alphas_host, double* betas_host, krcn_lanczos_info* info, hipStream_t s,
+                        bool enqueue_only = false);
 krcn_status lanczos_f32(krcn_csr* h, const float* w, const float* g, int m, int reorth, double tol, double l2,
-                        float* V, double* alphas_host, double* betas_host, krcn_lanczos_info* info, hipStream_t s);
+                        float* V, double* alphas_host, double* betas_host, krcn_lanczos_info* info, hipStream_t s,
+                        bool enqueue_only = false);
+
+// The results of a recurrence from the mapped block k_lz_final packed (state,
+// alphas[0..m), betas[0..m-1)), after the stream has passed it: the
+// reference's truncation rule (cubic.py:105-108) and return values.
+inline void lanczos_results(const krcn_csr* h, int m, double* alphas_host, double* betas_host,
+                            krcn_lanczos_info* info) {
+  const double* hb = h->hostres;
+  LanczosState stc;
+  std::memcpy(&stc, hb, sizeof(LanczosState));
+  const bool trunc = stc.done && stc.j_break < m - 2;
+  const int m_eff = trunc ? stc.j_break + 1 : m;
+  for (int i = 0; i < m; ++i) alphas_host[i] = i < m_eff ? hb[4 + i] : 0.0;
+  for (int i = 0; i + 1 < m; ++i) betas_host[i] = i < m_eff - 1 ? hb[4 + m + i] : 0.0;
+  info->m_eff = m_eff;
+  info->breakdown = stc.done;
+  info->j_break = stc.done ? stc.j_break : -1;
+  info->hvps = (stc.done ? stc.j_break + 1 : (m - 1)) + 1;
+  info->beta_last = stc.beta_last;
+  info->gnorm = stc.gnorm;
+}
+
+// The workspace of krcn_cubic_tridiag / krcn_crn_step (krcn_crn.hip): allocated
+// by krcn_csr_reserve and by the first of those calls.
+krcn_status ensure_crn_ws(krcn_csr* h);
 
 #include "krcn_pass.hpp"

@@ -2,8 +2,9 @@
 #include "krcn_lanczos_impl.hpp"
 
 krcn_status lanczos_f64(krcn_csr* h, const double* w, const double* g, int m, int reorth, double tol, double l2,
-                        double* V, double* alphas_host, double* betas_host, krcn_lanczos_info* info, hipStream_t s) {
-  return lanczos_impl<double>(h, w, g, m, reorth, tol, l2, V, alphas_host, betas_host, info, s);
+                        double* V, double* alphas_host, double* betas_host, krcn_lanczos_info* info, hipStream_t s,
+                        bool enqueue_only) {
+  return lanczos_impl<double>(h, w, g, m, reorth, tol, l2, V, alphas_host, betas_host, info, s, enqueue_only);
 }
 
 #ifdef KRCN_WIN_TIMING

@@ -230,7 +230,7 @@ static bool pack_env_ok() {
 template <typename T>
 static krcn_status lanczos_impl(krcn_csr* h, const T* w, const T* g, int m, int reorth, double tol,
                                 double l2, T* V, double* alphas_host, double* betas_host,
-                                krcn_lanczos_info* info, hipStream_t s_call) {
+                                krcn_lanczos_info* info, hipStream_t s_call, bool enqueue_only) {
   hipStream_t s = s_call;   // the capture stream while a graph is being recorded
   const int64_t d = h->d, n = h->n;
   CHK(plans_for_compute(h));
@@ -314,7 +314,7 @@ static krcn_status lanczos_impl(krcn_csr* h, const T* w, const T* g, int m, int 
   // hipGraph: recorded on the handle's private stream the second time the same
   // arguments arrive, launched on the caller's stream from then on (one
   // submission per call instead of 2-4 dependent launches per Lanczos step).
-  const bool graph = h->graph && h->shard == KRCN_SHARD_NONE && !h->prof;
+  const bool graph = h->graph && h->shard == KRCN_SHARD_NONE && !h->prof && !enqueue_only;
   const uint64_t key[krcn_csr::kGraphKey] = {uint64_t(uintptr_t(w)), uint64_t(uintptr_t(g)), uint64_t(uintptr_t(V)),
                                              uint64_t(uintptr_t(W)), uint64_t(m), uint64_t(reorth), bits(tol),
                                              bits(l2), h->ws_gen, uint64_t(sizeof(T))};
@@ -647,6 +647,9 @@ static krcn_status lanczos_impl(krcn_csr* h, const T* w, const T* g, int m, int 
   }
   return KRCN_OK;
   };
+  // krcn_crn_step: the launches alone, eager and outside the placement search;
+  // the caller synchronises and reads the results block (lanczos_results)
+  if (enqueue_only) return enqueue();
   bool lzp_timed = false;
   if (replay) {
     HIPCHK(hipGraphLaunch(h->gexec, s_call));
@@ -680,22 +683,10 @@ static krcn_status lanczos_impl(krcn_csr* h, const T* w, const T* g, int m, int 
   }
   // the recurrence results: k_lz_final packed the state, alphas[0..m) and
   // betas[0..m-1) straight into the mapped host block (no copy launch)
-  const double* hb = h->hostres;
   if (2 * m + 3 > kLzOut) return fail(KRCN_ERR_UNSUPPORTED, "krcn_lanczos: m > 2044 not supported");
   HIPCHK(hipStreamSynchronize(s));
   CHK(lzp_done(h, lzp_timed));
-  LanczosState stc;
-  std::memcpy(&stc, hb, sizeof(LanczosState));
-  const bool trunc = stc.done && stc.j_break < m - 2;
-  const int m_eff = trunc ? stc.j_break + 1 : m;
-  for (int i = 0; i < m; ++i) alphas_host[i] = i < m_eff ? hb[4 + i] : 0.0;
-  for (int i = 0; i + 1 < m; ++i) betas_host[i] = i < m_eff - 1 ? hb[4 + m + i] : 0.0;
-  info->m_eff = m_eff;
-  info->breakdown = stc.done;
-  info->j_break = stc.done ? stc.j_break : -1;
-  info->hvps = (stc.done ? stc.j_break + 1 : (m - 1)) + 1;
-  info->beta_last = stc.beta_last;
-  info->gnorm = stc.gnorm;
+  lanczos_results(h, m, alphas_host, betas_host, info);
   return KRCN_OK;
 }
 

@@ -764,5 +764,6 @@ extern "C" krcn_status krcn_csr_reserve(krcn_csr* h, int m_max, int reorth) {
   CHK(ensure_plans(h));
   CHK(agree_rows(h));   // (outside the build lock: virtual ranks are threads of one process)
   if (reorth) CHK(reserve_reorth(h, m_max));
+  if (h->shard == KRCN_SHARD_NONE) CHK(ensure_crn_ws(h));   // krcn_crn_step's state and subproblem vectors
   return KRCN_OK;
 }

@@ -53,6 +53,14 @@ class LanczosInfo(ctypes.Structure):
                 ("beta_last", ctypes.c_double), ("gnorm", ctypes.c_double)]
 
 
+class CrnInfo(ctypes.Structure):
+    """krcn_crn_info (include/krcn.h)."""
+    _fields_ = [("accepted", ctypes.c_int), ("trials", ctypes.c_int), ("solver_it", ctypes.c_int),
+                ("solver_status", ctypes.c_int), ("reg_coef", ctypes.c_double), ("lam", ctypes.c_double),
+                ("model_decrease", ctypes.c_double), ("value_new", ctypes.c_double),
+                ("dx_norm", ctypes.c_double), ("lanczos", LanczosInfo)]
+
+
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
 _i64 = ctypes.c_int64
@@ -103,6 +111,9 @@ SIGNATURES = {
     "krcn_comm_create_virtual": [_i, _i, ctypes.POINTER(_vp)],
     "krcn_comm_allreduce": [_vp, _i, _vp, _i64, _vp],
     "krcn_cg_solve": [_vp, _vp, _vp, _d, _d, _i, _vp, ctypes.POINTER(CgInfo), _vp],
+    "krcn_cubic_tridiag": [_vp, _i, _dp, _dp, _d, _d, _d, _d, _i, _dp, ctypes.POINTER(CrnInfo), _vp],
+    "krcn_crn_step": [_vp, _vp, _vp, _vp, _d, _i, _i, _d, _d, _d, _d, _d, _d, _i, _i, _vp, _vp, _vp, _dp, _dp,
+                      ctypes.POINTER(CrnInfo), _vp],
     "krcn_vctx_create": [_i, ctypes.POINTER(_vp)],
     "krcn_vctx_destroy": [_vp],
     "krcn_lz_ext_step": [_vp, _i, _i64, _vp, _vp, _vp, _d, _vp, _dp, _vp],

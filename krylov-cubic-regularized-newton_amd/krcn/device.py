@@ -394,6 +394,63 @@ class DeviceCSR:
              _ptr(out), _stream(self.device))
         return out
 
+    # -- the Krylov-CRN step on the device -----------------------------------
+    def cubic_tridiag(self, alphas, betas, gnorm, M, r0=0.1, eps=1e-8, it_max=100):
+        """The cubic subproblem over T = tridiag(betas, alphas, betas) with
+        g = gnorm e1, solved on the device in fp64 (krcn_cubic_tridiag; what
+        optimizer.cubic.cubic_solver_root_tridiag computes on the host).
+        Returns (s, info): s a numpy (m,) array, info a _lib.CrnInfo whose
+        solver_it / solver_status / lam / model_decrease / reg_coef are set
+        (status 0 ok, 1 T + lam I not positive definite, 2 derivative zero,
+        3 it_max reached with the last iterate returned)."""
+        al = np.ascontiguousarray(alphas, dtype=np.float64).reshape(-1)
+        be = np.ascontiguousarray(betas, dtype=np.float64).reshape(-1)
+        m = len(al)
+        if len(be) != max(m - 1, 0):
+            raise ValueError("betas must have len(alphas) - 1 entries")
+        s = np.zeros(max(m, 1), dtype=np.float64)
+        info = _lib.CrnInfo()
+        call("krcn_cubic_tridiag", self._h, m, al.ctypes.data_as(_lib._dp),
+             be.ctypes.data_as(_lib._dp) if m > 1 else None, float(gnorm), float(M), float(r0), float(eps),
+             int(it_max), s.ctypes.data_as(_lib._dp), ctypes.byref(info), _stream(self.device))
+        return s[:m], info
+
+    def crn_step(self, x, b, value, m, reg_coef, Ax=None, V=None, reorth=False, tol=1e-6, l2=0.0, ls_beta=0.5,
+                 r0=0.1, solver_eps=1e-8, solver_it_max=100, max_trials=20, x_new=None, Ax_new=None):
+        """One Krylov-CRN step from x with f(x) = value behind one library call
+        (krcn_crn_step): gradient, weights, Lanczos, then the backtracking line
+        search with the subproblem and the accept / reject test on the device.
+        Ax is X x when the caller has it.  Returns (x_new, Ax_new, alphas,
+        betas, info): the iterate the step keeps and its product with X (device
+        tensors), the recurrence's alphas / betas as lanczos() returns them,
+        and a _lib.CrnInfo (accepted, trials, solver_it, solver_status,
+        reg_coef, lam, model_decrease, value_new, dx_norm, lanczos)."""
+        m = int(m)
+        if m < 1:
+            raise ValueError("m must be >= 1")
+        self._check(x, self.d, "x")
+        self._check(b, self.n, "b")
+        if Ax is not None:
+            self._check(Ax, self.n, "Ax")
+        if V is None:
+            V = torch.empty((m, self.d), dtype=self.dtype, device=self.device)
+        elif (V.dtype != self.dtype or V.device != self.device or not V.is_contiguous()
+              or tuple(V.shape) != (m, self.d)):
+            raise ValueError(f"V must be a contiguous ({m}, {self.d}) {self.dtype} tensor on {self.device}")
+        x_new = self.empty_d() if x_new is None else self._check(x_new, self.d, "x_new")
+        Ax_new = self.empty_n() if Ax_new is None else self._check(Ax_new, self.n, "Ax_new")
+        if reorth and m > self._reorth_m and self.shard_mode == _lib.KRCN_SHARD_NONE:
+            self.reserve(m, reorth=True)
+        al = np.zeros(m, dtype=np.float64)
+        be = np.zeros(max(m - 1, 1), dtype=np.float64)
+        info = _lib.CrnInfo()
+        call("krcn_crn_step", self._h, _ptr(x), _ptr(b), _ptr(Ax), float(value), m, int(bool(reorth)), float(tol),
+             float(l2), float(reg_coef), float(ls_beta), float(r0), float(solver_eps), int(solver_it_max),
+             int(max_trials), _ptr(V), _ptr(x_new), _ptr(Ax_new), al.ctypes.data_as(_lib._dp),
+             be.ctypes.data_as(_lib._dp), ctypes.byref(info), _stream(self.device))
+        me = info.lanczos.m_eff
+        return x_new, Ax_new, al[:me], be[:max(me - 1, 0)], info
+
     # -- vector helpers ----------------------------------------------------
     def _space_len(self, space):
         return self.n if space == _lib.KRCN_SPACE_N else self.d

@@ -3,9 +3,13 @@
 Hot path (north_star): `Lanczos` + the logistic HVP run as hand-written gfx950
 kernels through libkrcn; the recurrence's control state (alpha, beta, the
 absolute 1e-6 breakdown test) stays on the device and only the m alphas / m-1
-betas come back.  The m x m tridiagonal cubic subproblem stays on the host, as
-in the reference, but as O(m) tridiagonal LDL^T solves (LAPACK dpttrf/dpttrs)
-instead of a dense Cholesky per Newton evaluation (cubic_solver_root_tridiag).
+betas come back.  The m x m tridiagonal cubic subproblem stays on the host by
+default, as in the reference, but as O(m) tridiagonal LDL^T solves (LAPACK
+dpttrf/dpttrs) instead of a dense Cholesky per Newton evaluation
+(cubic_solver_root_tridiag).  Cubic_Krylov_LS(device_step=True) runs the whole
+step behind one library call instead (krcn_crn_step): the same subproblem in
+one workgroup on the device and the line search's accept / reject test in a
+device kernel, with the backtracking trials enqueued in guarded batches.
 
 The comparison methods of cubic_newton.py run on the same device kernels:
 Cubic_LS (full-space CRN: "CG" solves with device conjugate gradients on the
@@ -211,11 +215,22 @@ class Cubic_Krylov_LS(Optimizer):
     of the reference's default is outside the hot path); subspace_dim: Krylov
     dimension m; solver_eps: tolerance of the host subproblem; beta:
     backtracking factor.  Build-only extras: reorth (CGS2 in Lanczos), tol
-    (absolute breakdown threshold, 1e-6 as cubic.py:98)."""
+    (absolute breakdown threshold, 1e-6 as cubic.py:98), device_step (one
+    krcn_crn_step call per step: the subproblem and the line search's decision
+    run on the device; unsharded losses and the tridiagonal subproblem only).
+    With device_step the loss's f_opt / x_opt follow the iterate each step
+    keeps, not the rejected trials (their vectors are overwritten on the
+    device), and the stopping test reads the step length the call reports."""
 
     def __init__(self, reg_coef=None, subspace_dim=100, solver_eps=1e-8, beta=0.5, *args,
-                 reorth=False, breakdown_tol=1e-6, dense_subproblem=False, **kwargs):
+                 reorth=False, breakdown_tol=1e-6, dense_subproblem=False, device_step=False, **kwargs):
         super().__init__(*args, **kwargs)
+        if device_step and dense_subproblem:
+            raise ValueError("device_step=True solves the tridiagonal subproblem: dense_subproblem must be False")
+        if device_step and getattr(self.loss, "shard", None) is not None:
+            raise NotImplementedError("device_step=True is implemented for unsharded problems")
+        self.device_step = bool(device_step)
+        self._dx_norm = None
         self.solver_it = 0
         self.subspace_dim = subspace_dim
         self.solver_eps = solver_eps
@@ -239,6 +254,8 @@ class Cubic_Krylov_LS(Optimizer):
     def step(self):
         """One Krylov-CRN step (cubic.py:265-309): grad -> Lanczos -> host cubic
         subproblem over T -> x + V s -> backtracking (at most 20 trials)."""
+        if self.device_step:
+            return self._step_on_device()
         loss = self.loss
         X = loss.device_matrix
         if self.value is None:
@@ -269,6 +286,43 @@ class Cubic_Krylov_LS(Optimizer):
         self.r0 = r0_new
         self.solver_it += solver_it
 
+    def _step_on_device(self):
+        """The same step as one krcn_crn_step call; the state afterwards is the
+        host path's (x, reg_coef, value, r0, solver_it, last_lanczos, hess,
+        grad) and the loss's cache holds X x_new for the new iterate."""
+        loss = self.loss
+        X = loss.device_matrix
+        if self.value is None:
+            self.value = loss.value(self.x)
+        x_new, Ax_new, alphas, betas, info = X.crn_step(
+            self.x, loss._b_dev, self.value, self.subspace_dim, self.reg_coef, Ax=loss._device_Ax(self.x),
+            V=self._basis(), reorth=self.reorth, tol=self.breakdown_tol, l2=float(loss.l2), ls_beta=self.beta,
+            r0=self.r0, solver_eps=self.solver_eps, max_trials=20)
+        self.last_lanczos = info.lanczos
+        self.hess = np.diag(alphas) + np.diag(betas, -1) + np.diag(betas, 1)
+        e1 = np.zeros(len(alphas))
+        e1[0] = 1
+        self.grad = info.lanczos.gnorm * e1
+        if info.solver_status == 1:
+            raise la.LinAlgError("T + lam I is not positive definite")
+        if info.solver_status == 2:
+            raise ArithmeticError("cubic subproblem: the derivative of phi was zero")
+        loss.adopt_product(x_new, Ax_new)
+        loss.note_value(x_new, info.value_new)
+        self.x = x_new
+        self.reg_coef = info.reg_coef
+        self.value = info.value_new
+        self.r0 = info.lam
+        self.solver_it += info.solver_it
+        self._dx_norm = info.dx_norm
+
+    def _keep_previous_iterate(self):
+        if not self.device_step:
+            super()._keep_previous_iterate()
+
+    def _step_length(self):
+        return self._dx_norm if self.device_step else super()._step_length()
+
     def _subproblem(self, alphas, betas, reg_coef):
         """The m x m cubic subproblem over T = tridiag(betas, alphas, betas)
         (cubic.py:285-286): O(m) tridiagonal solves, or the reference's dense
@@ -282,6 +336,7 @@ class Cubic_Krylov_LS(Optimizer):
         super().init_run(*args, **kwargs)
         self.trace.solver_its = [0]
         self.loss.reset()
+        self._dx_norm = None
 
     def update_trace(self):
         super().update_trace()

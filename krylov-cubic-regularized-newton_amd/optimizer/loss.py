@@ -328,6 +328,22 @@ class LogisticRegression(Oracle):
             self.x_last = x
         return Ax
 
+    def adopt_product(self, x, Ax):
+        """Make Ax the cached product of the device iterate x (a step that
+        formed X x itself hands it over, so the next gradient runs no matvec)."""
+        if not self.store_mat_vec_prod:
+            return
+        self._mat_vec_prod = Ax
+        self._w = None
+        self._cache_x, self._cache_ver, self._cache_np = x, x._version, None
+        self.x_last = x
+
+    def note_value(self, x, val):
+        """Best-iterate tracking (loss.py:66-73) for a value computed elsewhere."""
+        if val < self.f_opt:
+            self.x_opt = x.clone()
+            self.f_opt = val
+
     def _weights_for(self, x):
         Ax = self._device_Ax(x)
         if self.store_mat_vec_prod and Ax is self._mat_vec_prod:

@@ -81,8 +81,7 @@ class Optimizer:
         shown = 0
         try:
             while not self.check_convergence():
-                if self.tolerance > 0:
-                    self.x_old_tol = self.loss.copy_vector(self.x)
+                self._keep_previous_iterate()
                 self.step()
                 self.save_checkpoint()
                 now = self._progress_value(by_iterations)
@@ -100,10 +99,23 @@ class Optimizer:
         if self.line_search is not None:
             done = done or self.line_search.it >= self.ls_it_max
         done = done or (time.perf_counter() - self.t_start >= self.t_max)
-        if self.tolerance > 0 and self.x_old_tol is not None:
-            done = done or self.loss.norm_diff(self.x, self.x_old_tol) < self.tolerance
+        if self.tolerance > 0:
+            length = self._step_length()
+            if length is not None:
+                done = done or length < self.tolerance
         agree = getattr(self.loss, "any_rank", None)
         return agree(done) if agree is not None else done
+
+    def _keep_previous_iterate(self):
+        """Before a step: what _step_length needs afterwards (a copy of x)."""
+        if self.tolerance > 0:
+            self.x_old_tol = self.loss.copy_vector(self.x)
+
+    def _step_length(self):
+        """||x_k - x_{k-1}|| of the last step, None before the first."""
+        if self.x_old_tol is None:
+            return None
+        return self.loss.norm_diff(self.x, self.x_old_tol)
 
     def step(self):
         pass
