@@ -273,7 +273,11 @@ krcn_status krcn_csr_plan_value_bytes(krcn_csr* h, int* out2_host);
 /* Execution plan summary (builds the plan if needed):
  * out8_host = {slices, lanes, tiles, grid} of pass 1 (X) then pass 2 (X^T);
  * a sorted-tile pass reports its slice count negated; a dense pass reports
- * {slices, lanes, row groups, grid}. */
+ * {slices, lanes, row groups, grid}.  A window plan reports the tiles of one
+ * slice: ceil(rows / R) for fixed tiles of R rows; for a window-slices plan
+ * whose tiles are cut from the data (as many rows, up to 64, as fill one
+ * 256-nonzero chunk; long streams of short rows) the count of the slice with
+ * the most tiles. */
 krcn_status krcn_csr_plan_info(krcn_csr* h, int* out8_host);
 /* Format of each pass's plan (KRCN_PLAN_*): out2_host = {pass 1, pass 2}. */
 krcn_status krcn_csr_plan_format(krcn_csr* h, int* out2_host);

@@ -120,7 +120,7 @@ constexpr int kWinChunk = 256;               // nonzeros per staging step (4 per
 constexpr int kWinTMax = 6;                  // accumulate mode: tiles per wave (register sums)
 constexpr int kWinPad = kWinChunk + 8;       // array padding: unconditional chunk loads stay in bounds
 constexpr int kWinRing = 3;                  // chunk slots in flight per wave (slices mode)
-constexpr int kWinBatch = 58;                // slices mode: tiles per batch of tile bases (64 - the look-ahead)
+constexpr int kWinBatch = 26;                // slices mode: tiles per batch of tile bases and rows (32 - the look-ahead)
 // LDS: window + 16 slabs of kWinChunk + the reduction scratch must fit 160 KiB
 template <typename T> struct WinGeom {
   static constexpr int kSlabBytes = kWinWaves * kWinChunk * int(sizeof(T));

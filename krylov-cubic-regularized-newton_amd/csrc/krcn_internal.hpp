@@ -236,14 +236,16 @@ struct PlanFields {
   void* gval = nullptr;       //               value, same (tile-sorted) order
   int* tmid = nullptr;        // sorted tiles: first single-long-row tile of each group
   // LDS-window formats (k_window_pass; window-accum: every block walks all slices of its tile range, no partials)
-  int R = 64;                 //   rows per tile (one lane per row)
+  int R = 64;                 //   rows per tile (one lane per row); slices mode with data-cut tiles: the cap, 64
   int W = 0;                  //   slice width (window entries)
   int stride = 1;             //   segment slots per block
   int kpb = 0;                //   slices mode: blocks per slice when not a power of two (0: block = slice + S chunk)
   int nseg = 0;
   unsigned short* widx = nullptr;  // slice-local 16-bit column offsets (slice-major CSR order)
   WinSeg* segs = nullptr;     // per-block segment lists: block b runs segs[b * stride + i]
-  int* tb = nullptr;          // compact row pointers: tile bases (S x (ntiles + 1))
+  int* tb = nullptr;          // compact row pointers: tile bases (S x (ntiles + 1)); slices mode: every slice's
+                              //   bases are followed by its tiles' row starts (S x 2 (ntiles + 1); ntiles: the
+                              //   largest slice's count)
   unsigned short* ro = nullptr;   //   row ends relative to the tile base (S x rows)
   // jagged lane-per-row format (k_jag_pass; S, W, widx, own_val, grid)
   int jK = 0;                 //   groups per wave (units per wave and slice)

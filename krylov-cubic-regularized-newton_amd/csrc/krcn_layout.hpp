@@ -365,13 +365,46 @@ inline WinShape win_shape(int64_t cols, int accum) {
 
 // Step 2, from the slice-major row pointers hp (S * rows + 1): the tiles and
 // every block's segment list.
+//   accumulate: tiles of R rows, the same in every slice (tile t: rows
+//           [t R, t R + R)); ntiles = ceil(rows / R).
+//   slices: every slice has its own tiles, given by their row starts (trow).
+//           Fixed tiles of R rows are one case (every slice alike).  Data-cut
+//           tiles (`datacut`) are the other: a tile is the longest run of
+//           consecutive rows of its slice with at most kWinTileRows rows whose
+//           nonzeros, counted from the 4-aligned element win_load starts at,
+//           fit one staging chunk ((e0 & 3) + nnz <= kWinChunk); a row that
+//           alone exceeds a chunk is its own tile (the extra-chunk loop).
+//           Tile counts then differ from slice to slice: tcount holds them,
+//           ntiles is the largest (the stride of tb / trow, and what
+//           krcn_csr_plan_info reports), R the lane cap kWinTileRows.
+constexpr int kWinTileRows = 64;   // rows of a tile: one lane per row
 struct WinLayout {
   krcn_status refused = KRCN_OK;
   int R = 64, ntiles = 0, stride = 1, grid = 1, kpb = 0;
+  bool datacut = false;
   std::vector<WinSeg> segs;   // block b runs segs[b * stride + i]
   std::vector<int> cut;       // accumulate: grid + 1 tile cuts (block b owns tiles [cut[b], cut[b + 1]))
+  std::vector<int> trow;      // slices: S x (ntiles + 1) tile row starts (past a slice's count: rows)
+  std::vector<int> tcount;    // slices: S tile counts
 };
-inline WinLayout win_layout(const WinShape& sh, int rows, int64_t nnz, const int* hp) {
+// Row starts of the data-cut tiles of one slice (rp: its rows + 1 absolute row
+// pointers), with the closing entry `rows`.
+inline void win_cut_tiles(const int* rp, int rows, std::vector<int>& out) {
+  out.clear();
+  int r = 0;
+  while (r < rows) {
+    out.push_back(r);
+    const int64_t lo = rp[r] & ~3;
+    int r1 = r + 1;
+    while (r1 < rows && r1 - r < kWinTileRows && int64_t(rp[r1 + 1]) - lo <= kWinChunk) ++r1;
+    r = r1;
+  }
+  out.push_back(rows);
+}
+// forced: the tiling a caller asks for instead of the rule's (tuning builds'
+// KRCN_WIN_R, the layout tests): 16 / 32 / 64 fixed rows, 1 data-cut tiles
+// (slices mode), 0 the rule.
+inline WinLayout win_layout(const WinShape& sh, int rows, int64_t nnz, const int* hp, int forced = 0) {
   const int S = sh.S, kpb = sh.kpb;
   const bool accum = sh.kind == KRCN_PLAN_WINDOW_ACCUM;
   WinLayout L;
@@ -383,32 +416,71 @@ inline WinLayout win_layout(const WinShape& sh, int rows, int64_t nnz, const int
   // (profiles/r03_news20_winR.txt); the few tiles past 256 take one extra chunk.
   const double mean = double(nnz) / (double(rows) * double(S));
   L.R = mean * 64.0 <= 0.95 * kWinChunk ? 64 : mean * 32.0 <= 0.95 * kWinChunk ? 32 : 16;
-  {
-    const int r = tuning_value("KRCN_WIN_R", 0);   // A/B knob: rows per tile (16 / 32 / 64)
-    if (r == 16 || r == 32 || r == 64) L.R = r;
-  }
+  // A/B knob: 16 / 32 / 64 rows per tile, 1 data-cut tiles (slices mode)
+  if (forced == 0) forced = tuning_value("KRCN_WIN_R", 0);
+  if (forced == 16 || forced == 32 || forced == 64) L.R = forced;
   const int R = L.R;
-  const int ntiles = (rows + R - 1) / R;
+  const int nfixed = (rows + R - 1) / R;
+  // Slices mode, data-cut tiles.  A fixed R below 64 leaves the chunks partly
+  // empty: the rule above only knows 16 / 32 / 64, and where 64 mean rows pass
+  // a chunk it halves them (news20 at 85 slices: 5.35 nonzeros per row and
+  // slice, 171 of 256 slots a tile), yet every tile pays its loads, gathers,
+  // slab writes and row walk for all 256.  Tiles cut from the data fill the
+  // chunk (news20: 0.67 -> 0.985, 625 -> ~424 tiles a slice).  They are taken
+  // where the fixed rule gives R < 64 and the fixed tiling gives a slice's
+  // blocks kWinWaves * kWinRing tiles each on average (the cuts balance
+  // nonzeros, so a block's count scatters round that mean): a wave with
+  // fewer than kWinRing tiles never fills its ring, the stream is start-up
+  // and not fill.  At R = 64 the fixed tiles are already row-capped.
+  L.datacut = !accum && (forced == 1 || (forced == 0 && R < kWinTileRows &&
+                                         int64_t(nfixed) >= int64_t(kpb) * kWinWaves * kWinRing));
+  if (L.datacut) L.R = kWinTileRows;
+  int ntiles = nfixed;
+  if (!accum) {
+    std::vector<std::vector<int>> starts(static_cast<size_t>(S));
+    for (int sl = 0; sl < S; ++sl) {
+      std::vector<int>& st = starts[size_t(sl)];
+      if (L.datacut) {
+        win_cut_tiles(hp + size_t(sl) * rows, rows, st);
+      } else {
+        for (int t = 0; t < nfixed; ++t) st.push_back(t * R);
+        st.push_back(rows);
+      }
+    }
+    if (L.datacut) {
+      ntiles = 0;
+      for (int sl = 0; sl < S; ++sl) ntiles = std::max(ntiles, int(starts[size_t(sl)].size()) - 1);
+    }
+    L.tcount.resize(size_t(S));
+    L.trow.assign(size_t(S) * (size_t(ntiles) + 1), rows);
+    for (int sl = 0; sl < S; ++sl) {
+      const std::vector<int>& st = starts[size_t(sl)];
+      L.tcount[size_t(sl)] = int(st.size()) - 1;
+      std::copy(st.begin(), st.end(), L.trow.begin() + size_t(sl) * (size_t(ntiles) + 1));
+    }
+  }
   L.ntiles = ntiles;
+  auto tcount = [&](int sl) { return accum ? ntiles : L.tcount[size_t(sl)]; };
   auto tnnz = [&](int sl, int t) -> int64_t {
     const int* rp = hp + size_t(sl) * rows;
-    const int r0 = t * R, r1 = std::min(rows, r0 + R);
+    const int* tr = accum ? nullptr : L.trow.data() + size_t(sl) * (size_t(ntiles) + 1);
+    const int r0 = accum ? t * R : tr[t], r1 = accum ? std::min(rows, r0 + R) : tr[t + 1];
     return int64_t(rp[r1]) - rp[r0];
   };
   // compact row pointers (16-bit row ends inside a tile): every tile of every
   // slice must hold < 65536 nonzeros, else the format does not apply
   for (int sl = 0; sl < S; ++sl)
-    for (int t = 0; t < ntiles; ++t)
+    for (int t = 0; t < tcount(sl); ++t)
       if (tnnz(sl, t) > 65535) {
         L.refused = fail(KRCN_ERR_UNSUPPORTED, "window plan: a tile holds > 65535 nonzeros");
         return L;
       }
-  // cut [0, ntiles) into B ranges of equal cost(t) (prefix-sum cuts)
-  auto cut_ranges = [&](int B, auto&& cost) {
-    std::vector<int64_t> pre(ntiles + 1, 0);
-    for (int t = 0; t < ntiles; ++t) pre[t + 1] = pre[t] + cost(t);
+  // cut [0, n) into B ranges of equal cost(t) (prefix-sum cuts)
+  auto cut_ranges = [&](int n, int B, auto&& cost) {
+    std::vector<int64_t> pre(size_t(n) + 1, 0);
+    for (int t = 0; t < n; ++t) pre[t + 1] = pre[t] + cost(t);
     std::vector<int> cut(B + 1, 0);
-    balanced_cuts(pre, ntiles, B, cut.data());
+    balanced_cuts(pre, n, B, cut.data());
     return cut;
   };
   if (accum) {
@@ -420,7 +492,7 @@ inline WinLayout win_layout(const WinShape& sh, int rows, int64_t nnz, const int
     const int cap = kWinWaves * kWinTMax;   // tiles per block (register sums)
     int B = std::max(1, tuning_value("KRCN_WIN_ACC_B", kNumCUs));   // A/B knob: first grid tried
     for (;;) {
-      L.cut = cut_ranges(B, cost);
+      L.cut = cut_ranges(ntiles, B, cost);
       int mx = 0;
       for (int b = 0; b < B; ++b) mx = std::max(mx, L.cut[b + 1] - L.cut[b]);
       if (mx <= cap || B >= 64 * kNumCUs) break;
@@ -443,7 +515,7 @@ inline WinLayout win_layout(const WinShape& sh, int rows, int64_t nnz, const int
     // run): the fused Lanczos prologue has it store its share of that slice
     std::vector<std::vector<int>> cuts(static_cast<size_t>(S));
     for (int sl = 0; sl < S; ++sl)
-      cuts[size_t(sl)] = cut_ranges(kpb, [&](int t) { return tnnz(sl, t) + kWinTileCost; });
+      cuts[size_t(sl)] = cut_ranges(tcount(sl), kpb, [&](int t) { return tnnz(sl, t) + kWinTileCost; });
     L.segs.resize(size_t(S) * kpb);
     for (int b = 0; b < L.grid; ++b) {
       int sl = 0, c = 0;

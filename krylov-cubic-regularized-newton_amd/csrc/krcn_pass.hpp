@@ -155,9 +155,12 @@ inline void launch_window(const PassPlan& P, const Src& first, const E& ep, doub
       hipLaunchKernelGGL((k_window_pass<T, TS, decltype(rc)::value, Src, E, accum>), dim3(P.grid), dim3(kWinNT), 0, s,
                          wa, first, ep, parts);
     };
-    if (P.R == 16) launch(std::integral_constant<int, 16>{});
-    else if (P.R == 32) launch(std::integral_constant<int, 32>{});
-    else launch(std::integral_constant<int, 64>{});
+    // slices mode: the tiles' rows are plan data (they follow the bases in P.tb), one kernel with a lane cap of 64 whatever P.R
+    if constexpr (accum) {
+      if (P.R == 16) return launch(std::integral_constant<int, 16>{});
+      if (P.R == 32) return launch(std::integral_constant<int, 32>{});
+    }
+    launch(std::integral_constant<int, 64>{});
   });
 }
 
@@ -343,8 +346,9 @@ inline krcn_status run_pass(PassPlan& P, const Src& first, const Src2& rest, con
 // folded in (krcn_window.hpp EpiSliceFold; tuning builds).
 inline bool fold_ok(const krcn_csr* h) {
   const PassPlan& P = h->p1;
+  // (uniform 32-row tiles only — the tile index is r0 / 32; a data-cut plan has R = 64 — and full-width plans)
   return h->fcnt && P.kind == KRCN_PLAN_WINDOW_SLICES && P.R == 32 && P.S <= 96 && P.ntiles <= h->pcap &&
-         P.vbytes == int(h->vs);   // (full-width plans only)
+         P.vbytes == int(h->vs);
 }
 template <typename T>
 inline krcn_status run_fold_pass1(krcn_csr* h, const SrcLzBeta<T>& src, const EpiSliceFold<T>& epi, hipStream_t s) {

@@ -254,10 +254,27 @@ static krcn_status build_window_as(PassPlan& P, const int* ptr, const int* idx, 
   CHK(plan_reloc(P, &P.widx, s));
   CHK(plan_reloc(P, &P.own_val, s));
   P.val = P.own_val;
-  CHK(P.own.alloc(&P.tb, sizeof(int) * size_t(S) * (wl.ntiles + 1)));
+  CHK(P.own.alloc(&P.tb, sizeof(int) * size_t(S) * (accum ? 1 : 2) * (wl.ntiles + 1)));
   CHK(P.own.alloc(&P.ro, sizeof(unsigned short) * std::max<size_t>(size_t(S) * rows, 1)));
-  hipLaunchKernelGGL(k_compact_rows, dim3(vec_grid(int64_t(S) * rows)), dim3(kNT), 0, s, S, rows, wl.R, wl.ntiles,
-                     P.ptr, P.tb, P.ro);
+  std::vector<int> tbr;   // (outlives the copy)
+  if (accum) {
+    hipLaunchKernelGGL(k_compact_rows, dim3(vec_grid(int64_t(S) * rows)), dim3(kNT), 0, s, S, rows, wl.R, wl.ntiles,
+                       P.ptr, P.tb, P.ro);
+  } else {
+    // the tiles are the layout's (fixed or data-cut): per slice the tiles' bases, then their row starts
+    const size_t n1 = size_t(wl.ntiles) + 1;
+    tbr.resize(size_t(S) * 2 * n1);
+    for (int sl = 0; sl < S; ++sl)
+      for (size_t t = 0; t < n1; ++t) {
+        const int r = wl.trow[size_t(sl) * n1 + t];
+        tbr[size_t(sl) * 2 * n1 + t] = hp[size_t(sl) * rows + r];
+        tbr[size_t(sl) * 2 * n1 + n1 + t] = r;
+      }
+    HIPCHK(hipMemcpyAsync(P.tb, tbr.data(), sizeof(int) * tbr.size(), hipMemcpyHostToDevice, s));
+    if (wl.ntiles > 0)
+      hipLaunchKernelGGL(k_compact_tiles, dim3(vec_grid(int64_t(S) * wl.ntiles)), dim3(kNT), 0, s, S, rows, wl.ntiles,
+                         P.ptr, P.tb, P.ro);
+  }
   LAUNCHCHK();
   HIPCHK(hipStreamSynchronize(s));
   // the kernels read the compact form only

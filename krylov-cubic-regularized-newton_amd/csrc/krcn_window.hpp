@@ -16,10 +16,14 @@
 //    element order, pads and geometry, values widened at the multiply) — and
 //    compact row pointers: a 32-bit base per (slice, tile) plus 16-bit row
 //    ends relative to it.
-//  * Tiles of R consecutive rows (R = 16/32/64, from the mean row length per
-//    slice); lane l of a wave owns row R t + l of tile t and sums its
-//    elements left to right (1 lane per row — these formats are chosen for
-//    short rows only).
+//  * Tiles of consecutive rows, at most 64; lane l of a wave owns row l of
+//    its tile and sums its elements left to right (1 lane per row — these
+//    formats are chosen for short rows only).  Accumulate mode: R rows a tile
+//    (R = 16/32/64, from the mean row length per slice), the same in every
+//    slice.  Slices mode: every slice's tiles are given by their row starts
+//    (WinArgs::tr) — fixed R-row tiles, or tiles cut from the data so that
+//    each fills one staging chunk (krcn_layout.hpp win_layout) — and one
+//    kernel with a lane cap of 64 runs either.
 //  * Segments {slice, t0, t1, flags}: block b runs segs[b * stride + i]
 //    (the first entry carries the count); wave w takes tiles t0 + w,
 //    t0 + w + 16, ...; kSegLoad loads the slice's window first, kSegFlush
@@ -61,9 +65,9 @@ constexpr int kWinRingAccum = KRCN_WIN_RING_ACCUM;   // (accumulate mode, regist
 #define KRCN_WIN_SUMU 8   // long rows: slab reads batched per lane (same add order: the same bits)
 #endif
 #ifndef KRCN_WIN_COOP
-#define KRCN_WIN_COOP 1   // very long runs of a slices-mode chunk summed by the whole wave (0: A/B, round 6)
+#define KRCN_WIN_COOP 1   // slices mode: very long rows of a slice summed by the whole wave (0: A/B, round 6)
 #endif
-constexpr int kWinCoopLen = 64;              // (KRCN_WIN_COOP) run length past which the wave sums it
+constexpr int kWinCoopLen = 64;              // (KRCN_WIN_COOP) row length in the slice past which the wave sums it
 #ifndef KRCN_WIN_FIRST
 #define KRCN_WIN_FIRST 1   // window stored before the first chunk loads go out
 #endif
@@ -71,15 +75,21 @@ constexpr int kWinCoopLen = 64;              // (KRCN_WIN_COOP) run length past 
 struct WinArgs {
   int rows, W, stride, S;
   int dbg;                       // diagnostic builds: stamp table (0 slices, 1 accumulate, 2 fused Lanczos)
-  int ntiles;                    // tiles of R rows per slice
+  int ntiles;                    // tiles per slice (slices mode: the largest slice's count)
   int64_t cols;
-  const int* tb;                 // tile bases: slice s, tile t begins at tb[s * (ntiles + 1) + t]
+  const int* tb;                 // tile bases: slice s, tile t begins at element win_tb(..)[t]; slices mode: and at
+                                 // row win_tb(..)[ntiles + 1 + t] (every slice: ntiles + 1 bases, then as many rows)
   const unsigned short* ro;      // row ends relative to their tile base: row r of slice s at ro[s * rows + r]
   const unsigned short* widx;    // slice-local column offsets
   const void* wval;
   const WinSeg* segs;            // block b: segs[b * stride + i]
   int kpb = 0;                   // slices mode: win_block_slice's mapping (0: block = slice + S chunk)
 };
+// The tile bases of one slice (accumulate: ntiles + 1 entries a slice; slices: the row starts follow them).
+template <bool kAccum>
+__device__ __forceinline__ const int* win_tb(const WinArgs& a, int slice) {
+  return a.tb + int64_t(slice) * ((kAccum ? 1 : 2) * (a.ntiles + 1));
+}
 
 typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
 
@@ -162,15 +172,16 @@ __device__ __forceinline__ void win_load(WinChunk<T, TS>& c, int c0, int e1, con
 
 // Gather x from the window, stage the products in the wave's slab, and add
 // this lane's row elements [beg, end) that fall in the chunk, in order.
+// coop / open: slices mode's long rows (below); open starts a tile as 0.
 template <typename T, typename TS>
 __device__ __forceinline__ T win_consume(const WinChunk<T, TS>& c, int beg, int end, const T* win, T* slab, int lane,
-                                         T s, bool coop = false) {
+                                         T s, bool coop, T& open) {
   const int e = c.base + 4 * lane;
   const unsigned short qi[4] = {c.q.x, c.q.y, c.q.z, c.q.w};
 #if defined(KRCN_WIN_ABL_NOSUM)        // ablation (timing only): no slab, no row walk
 #pragma unroll
   for (int i = 0; i < 4; ++i) s += T(c.v[i]) * win[e + i < c.hi ? qi[i] : 0];
-  (void)beg; (void)end; (void)slab;
+  (void)beg; (void)end; (void)slab; (void)coop; (void)open;
   return s;
 #else
 #pragma unroll
@@ -185,26 +196,38 @@ __device__ __forceinline__ T win_consume(const WinChunk<T, TS>& c, int beg, int 
   // of per element; the adds stay left to right (the same bits).  Short rows
   // (the uniform case, almost always) never enter it.  coop (slices mode over
   // S > 1 slices, whose partials are combined anyway, so not scipy's order):
-  // a run longer than kWinCoopLen is summed by the whole wave — strided
-  // partial sums, then a butterfly (every lane the same bits) — one run at a
-  // time, instead of by its lane alone while the others wait: skewed news20
-  // pass 1 41.5-41.7 -> 39.3-39.5 us, 11.4-11.5 k -> 11.8-12.2 k HVP/s
-  // (profiles/r06u_news20_skew_coop_ab.txt).  The uniform news20 never has
-  // such a run (5.35 elements a row and slice).  (Every run past 16 summed
-  // this way was slower, 41.3 -> 48.1 us: many medium runs went one by one.)
-  if (coop) {   // (wave-uniform) runs past kWinCoopLen: summed by the whole wave, one run at a time
-    unsigned long long longm = __ballot(pe - pb > kWinCoopLen);
+  // a row with more than kWinCoopLen elements in the slice is summed by the
+  // whole wave — strided partial sums, then a butterfly (every lane the same
+  // bits) — one row at a time, instead of by its lane alone while the others
+  // wait: skewed news20 pass 1 41.5-41.7 -> 39.3-39.5 us, 11.4-11.5 k ->
+  // 11.8-12.2 k HVP/s (profiles/r06u_news20_skew_coop_ab.txt; measured with
+  // the stripes cut per chunk).  The uniform news20 never has such a row
+  // (5.35 elements a row and slice).  (Every run past 16 summed this way was
+  // slower, 41.3 -> 48.1 us: many medium runs went one by one.)
+  // The sum is a function of the row alone, not of where tiles and chunks
+  // begin (plans tile the same rows differently: fixed or data-cut tiles):
+  // lane l adds the row's elements l, l + 64, ... counted from the row's
+  // first, in order through every chunk the row crosses — `open` carries the
+  // stripes to the tile's next chunk (only a chunk's last row goes on) — and
+  // the butterfly runs once, at the row's end.
+  if (coop) {   // (wave-uniform)
+    unsigned long long longm = __ballot(end - beg > kWinCoopLen && pe > pb);
     while (longm != 0ull) {
       const int L = __builtin_ctzll(longm);
       longm &= longm - 1ull;
       const int lb = __builtin_amdgcn_readlane(pb, L), le = __builtin_amdgcn_readlane(pe, L);
-      T part = T(0);
-      for (int q = lb + lane; q < le; q += 64) part += slab[q - c.base];
+      const int rb = __builtin_amdgcn_readlane(beg, L), re = __builtin_amdgcn_readlane(end, L);
+      T part = lb > rb ? open : T(0);
+      for (int q = lb + ((lane - (lb - rb)) & 63); q < le; q += 64) part += slab[q - c.base];
+      if (le < re) {
+        open = part;
+        continue;
+      }
 #pragma unroll
       for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off, 64);
       if (lane == L) s += part;
     }
-    if (pe - pb > kWinCoopLen) p = pe;   // this lane's run is in s
+    if (end - beg > kWinCoopLen) p = pe;   // this lane's row is summed above
   }
   if (__ballot(pe - p > 2 * KRCN_WIN_SUMU) != 0ull) {
     for (; p + KRCN_WIN_SUMU <= pe; p += KRCN_WIN_SUMU) {
@@ -273,18 +296,13 @@ __device__ __forceinline__ void unroll_while(std::integer_sequence<int, I...>, i
 
 // Wave-uniform bounds of tile t (clamped into [t0, t1)): rows [r0, r0 + nr),
 // nonzeros [e0, e1) of the slice's CSR (tb: this slice's tile bases).
+// Accumulate mode: tile t is rows [t R, t R + R) in every slice (set).  Slices
+// mode: the rows are the plan's (set_rows: tile row starts from a WinTiles
+// batch; fixed R-row tiles and data-cut tiles alike), R is only the lane cap.
 template <int R>
 struct TileB {
   int r0, nr, e0, e1;
-  __device__ __forceinline__ void load(const int* tb, int rows, int t, int t1) {
-    t = t < t1 ? t : t1 - 1;
-    t = t > 0 ? t : 0;
-    r0 = t * R;
-    nr = rows - r0 < R ? rows - r0 : R;
-    e0 = tb[t];
-    e1 = tb[t + 1];
-  }
-  // the same bounds from a WinTiles batch (no memory access)
+  // bounds from a WinTiles batch (no memory access)
   __device__ __forceinline__ void set(int rows, int t, int t1, int te0, int te1) {
     t = t < t1 ? t : t1 - 1;
     t = t > 0 ? t : 0;
@@ -293,24 +311,36 @@ struct TileB {
     e0 = te0;
     e1 = te1;
   }
+  __device__ __forceinline__ void set_rows(int tr0, int tr1, int te0, int te1) {
+    r0 = tr0;
+    nr = tr1 - tr0;
+    e0 = te0;
+    e1 = te1;
+  }
 };
 
-// Tile bases of a wave's tiles tw + 16 k, 64 tiles at a time: lane i holds
-// e0 / e1 of tile k = kb + i (clamped into the segment), one vector load for
-// all of them, read lane-wise (v_readlane) as the ring reaches each tile.
+// Tile bases of a wave's tiles tw + 16 k, a batch at a time, in two registers:
+// lane i holds e0 / e1 of tile k = kb + i (clamped into the segment), one
+// vector load each for all of them, read lane-wise (v_readlane) as the ring
+// reaches each tile.  kRows (slices mode): lanes 0-31 hold e0 / e1 of tile
+// kb + i and lanes 32-63 the row bounds r0 / r1 of the same 32 tiles (they
+// follow the slice's bases, `roff` entries on: one base pointer), so the rows
+// cost neither a register nor a load more than the bases.
 // Loading each tile's bases on its own and broadcasting them (readfirstlane)
 // made every tile wait for its load, and vmcnt retires in issue order: that
 // wait drained the whole ring of chunk loads once per tile (round 5, ISA of
 // k_window_pass).
 struct WinTiles {
-  int e0, e1, kb;
-  __device__ __forceinline__ void load(const int* tb, int tw, int t1, int kb_, int lane) {
+  int lo, hi, kb;   // lo / hi: e0 / e1 (lanes 32-63 under kRows: r0 / r1)
+  template <bool kRows>
+  __device__ __forceinline__ void load(const int* tb, int roff, int tw, int t1, int kb_, int lane) {
     kb = kb_;
-    int t = tw + kWinWaves * (kb + lane);
+    int t = tw + kWinWaves * (kb + (kRows ? lane & 31 : lane));
     t = t < t1 ? t : t1 - 1;
     t = t > 0 ? t : 0;   // an empty segment (t1 = 0: a slice with fewer tiles than its blocks) reads tile 0
-    e0 = tb[t];
-    e1 = tb[t + 1];
+    if (kRows && lane >= 32) t += roff;
+    lo = tb[t];
+    hi = tb[t + 1];
   }
 };
 
@@ -542,15 +572,16 @@ __device__ __forceinline__ void win_stream(int segno, const WinSeg& sg, const Wi
                                            T* slab, const Epi& epi, int wave, int lane,
                                            typename RedOf<Epi>::type& red, WinTiles tl) {
   const int rows = a.rows;
-  const int* tb = a.tb + int64_t(sg.slice) * (a.ntiles + 1);
+  const int* tb = win_tb<false>(a, sg.slice);
   const unsigned short* ro = a.ro + int64_t(sg.slice) * rows;
   const unsigned short* widx = a.widx;
   const TS* wval = static_cast<const TS*>(a.wval);
   const int tw = sg.t0 + wave;
   const int nt = sg.t1 - tw > 0 ? (sg.t1 - tw + kWinWaves - 1) / kWinWaves : 0;
   // tiles in batches of kWinBatch: the ring's look-ahead (5 tiles) stays
-  // inside one 64-lane batch of tile bases; a new batch (past 58 tiles of a
-  // wave, rare) restarts the ring behind its load
+  // inside one 32-tile batch of tile bases and rows; a new batch (past 26
+  // tiles of a wave: more than 416 tiles a block) restarts the ring behind
+  // its load
   const int nb = (nt + kWinBatch - 1) / kWinBatch;
   WinFold fold;   // (the slice-combine fold only: IsFoldEpi)
   if (nb == 0 && store_win) {   // a wave without tiles still takes part in the window store
@@ -561,10 +592,12 @@ __device__ __forceinline__ void win_stream(int segno, const WinSeg& sg, const Wi
   for (int bi = 0; bi < nb; ++bi) {
     const int kb = bi * kWinBatch;
     const int kn = nt - kb < kWinBatch ? nt - kb : kWinBatch;
-    if (bi > 0) tl.load(tb, tw, sg.t1, kb, lane);
-    auto bounds = [&](TileB<R>& b, int k) {   // tile kb + k, k < 64 (no memory access)
-      b.set(rows, tw + (kb + k) * kWinWaves, sg.t1, __builtin_amdgcn_readlane(tl.e0, k),
-            __builtin_amdgcn_readlane(tl.e1, k));
+    if (bi > 0) tl.load<true>(tb, a.ntiles + 1, tw, sg.t1, kb, lane);
+    // tile kb + k, k < 32, from the batch (no memory access): its elements when its chunk is loaded, its rows
+    // only when its row ends are (two tiles later), so few tiles' bounds are live at a time
+    auto bounds = [&](TileB<R>& b, int k) {
+      b.e0 = __builtin_amdgcn_readlane(tl.lo, k);
+      b.e1 = __builtin_amdgcn_readlane(tl.hi, k);
     };
     TileB<R> B0, B1, B2;
     bounds(B0, 0);
@@ -573,7 +606,8 @@ __device__ __forceinline__ void win_stream(int segno, const WinSeg& sg, const Wi
     WinChunk<T, TS> c0, c1, c2;
     RowRaw q0, q1, q2;
     typename Epi::Pre p0, p1, p2;
-    auto rows_of = [&](const TileB<R>& b, RowRaw& q, typename Epi::Pre& pr) {
+    auto rows_of = [&](TileB<R>& b, int k, RowRaw& q, typename Epi::Pre& pr) {
+      b.set_rows(__builtin_amdgcn_readlane(tl.lo, k + 32), __builtin_amdgcn_readlane(tl.hi, k + 32), b.e0, b.e1);
       q = tile_row_load<R>(b, ro, lane);
       const int r = b.r0 + lane;
       pr = epi.pre(r < rows ? r : rows - 1);
@@ -588,12 +622,12 @@ __device__ __forceinline__ void win_stream(int segno, const WinSeg& sg, const Wi
       lds_block_barrier();   // every wave is done with the previous window
       win_store<T>(tmp, win, sg.slice, a, rot);
     }
-    rows_of(B0, q0, p0);
+    rows_of(B0, 0, q0, p0);
     win_load(c0, B0.e0, B0.e1, widx, wval, lane);
     win_load(c1, B1.e0, B1.e1, widx, wval, lane);
     if (sw) lds_block_barrier();
 #else
-    rows_of(B0, q0, p0);
+    rows_of(B0, 0, q0, p0);
     win_load(c0, B0.e0, B0.e1, widx, wval, lane);
     win_load(c1, B1.e0, B1.e1, widx, wval, lane);
     if (sw) {
@@ -608,36 +642,32 @@ __device__ __forceinline__ void win_stream(int segno, const WinSeg& sg, const Wi
       int bg, en;
       tile_row_bounds<R>(b, q, lane, bg, en);
       const bool coop = KRCN_WIN_COOP && a.S > 1;
-      T s = win_consume(c, bg, en, win, slab, lane, T(0), coop);
+      T open = T(0);   // (coop: the partial sums of a long row that goes on in the tile's next chunk)
+      T s = win_consume(c, bg, en, win, slab, lane, T(0), coop, open);
       for (int cc = c.hi; cc < b.e1;) {          // tiles longer than one chunk
         WinChunk<T, TS> cx;
         win_load(cx, cc, b.e1, widx, wval, lane);
-        s = win_consume(cx, bg, en, win, slab, lane, s, coop);
+        s = win_consume(cx, bg, en, win, slab, lane, s, coop, open);
         cc = cx.hi;
       }
       if (k < kn && lane < b.nr) red += epi.row(b.r0 + lane, s, sg.slice, pr);
       if constexpr (IsFoldEpi<Epi>::value)
         if (k < kn) fold_after<T, R>(epi, fold, b.r0 / R, rows, lane);
     };
+    // B0 / B1 / B2: tiles k, k + 1, k + 2, then (as each is finished) k + 3, k + 4, k + 5
     for (int k = 0; k < kn; k += 3) {
-      TileB<R> B3;
-      bounds(B3, k + 3);
-      rows_of(B1, q1, p1);
+      rows_of(B1, k + 1, q1, p1);
       win_load(c2, B2.e0, B2.e1, widx, wval, lane);
       finish(c0, B0, q0, p0, k);
-      TileB<R> B4;
-      bounds(B4, k + 4);
-      rows_of(B2, q2, p2);
-      win_load(c0, B3.e0, B3.e1, widx, wval, lane);
+      bounds(B0, k + 3);
+      rows_of(B2, k + 2, q2, p2);
+      win_load(c0, B0.e0, B0.e1, widx, wval, lane);
       finish(c1, B1, q1, p1, k + 1);
-      TileB<R> B5;
-      bounds(B5, k + 5);
-      rows_of(B3, q0, p0);
-      win_load(c1, B4.e0, B4.e1, widx, wval, lane);
+      bounds(B1, k + 4);
+      rows_of(B0, k + 3, q0, p0);
+      win_load(c1, B1.e0, B1.e1, widx, wval, lane);
       finish(c2, B2, q2, p2, k + 2);
-      B0 = B3;
-      B1 = B4;
-      B2 = B5;
+      bounds(B2, k + 5);
     }
   }
   if constexpr (IsFoldEpi<Epi>::value) fold_drain<T, R>(epi, fold, rows, lane);
@@ -654,17 +684,15 @@ __device__ __forceinline__ void win_accum(int segno, const WinSeg& sg, const Win
   constexpr int K = kWinTMax;
   constexpr int D = kWinRingAccum;
   const int rows = a.rows;
-  const int* tb = a.tb + int64_t(sg.slice) * (a.ntiles + 1);
   const unsigned short* ro = a.ro + int64_t(sg.slice) * rows;
   const unsigned short* widx = a.widx;
   const TS* wval = static_cast<const TS*>(a.wval);
   const int nt = sg.t1 - sg.t0 - wave > 0 ? (sg.t1 - sg.t0 - wave + kWinWaves - 1) / kWinWaves : 0;
-  (void)tb;
   TileB<R> B[K];   // K <= 64: the whole segment from the batch (kb = 0)
 #pragma unroll
   for (int k = 0; k < K; ++k)
-    B[k].set(rows, sg.t0 + wave + k * kWinWaves, sg.t1, __builtin_amdgcn_readlane(tl.e0, k),
-             __builtin_amdgcn_readlane(tl.e1, k));
+    B[k].set(rows, sg.t0 + wave + k * kWinWaves, sg.t1, __builtin_amdgcn_readlane(tl.lo, k),
+             __builtin_amdgcn_readlane(tl.hi, k));
   WinChunk<T, TS> ring[D];
   RowRaw rq[D];
   typename Epi::Pre pre[D];
@@ -707,11 +735,12 @@ __device__ __forceinline__ void win_accum(int segno, const WinSeg& sg, const Win
     const WinChunk<T, TS>& cur = ring[k % D];
     int bg, en;
     tile_row_bounds<R>(B[k], rq[k % D], lane, bg, en);
-    T s = win_consume(cur, bg, en, win, slab, lane, acc[k]);
+    T none = T(0);   // (no whole-wave row sums: the rows carry across slices in scipy's order)
+    T s = win_consume(cur, bg, en, win, slab, lane, acc[k], false, none);
     for (int c = cur.hi; c < B[k].e1;) {
       WinChunk<T, TS> cx;
       win_load(cx, c, B[k].e1, widx, wval, lane);
-      s = win_consume(cx, bg, en, win, slab, lane, s);
+      s = win_consume(cx, bg, en, win, slab, lane, s, false, none);
       c = cx.hi;
     }
     if constexpr (FLUSH) {
@@ -830,8 +859,8 @@ __global__ __launch_bounds__(kWinNT, 1) void k_window_pass(WinArgs a, Src src, E
   if constexpr (!kAccum) win_block_slice(int(blockIdx.x), int(gridDim.x), a.S, a.kpb, slice0, chunk0);
   WinTiles tl;
   if constexpr (kAccum)
-    tl.load(a.tb + int64_t(sg.slice) * (a.ntiles + 1), sg.t0 + __builtin_amdgcn_readfirstlane(int(threadIdx.x) >> 6),
-            sg.t1, 0, int(threadIdx.x) & 63);
+    tl.template load<false>(win_tb<true>(a, sg.slice), 0, sg.t0 + __builtin_amdgcn_readfirstlane(int(threadIdx.x) >> 6),
+                            sg.t1, 0, int(threadIdx.x) & 63);
   T tmp[kPer];
   const T* x = nullptr;
   if constexpr (IsLzZ<Src>::value) {
@@ -925,8 +954,9 @@ __global__ __launch_bounds__(kWinNT, 1) void k_window_pass(WinArgs a, Src src, E
   }
   KRCN_WIN_STAMP(1);
   if constexpr (!kAccum)   // after the window fetch: its wait comes with the window's
-    tl.load(a.tb + int64_t(sg.slice) * (a.ntiles + 1), sg.t0 + __builtin_amdgcn_readfirstlane(int(threadIdx.x) >> 6),
-            sg.t1, 0, int(threadIdx.x) & 63);
+    tl.template load<true>(win_tb<false>(a, sg.slice), a.ntiles + 1,
+                           sg.t0 + __builtin_amdgcn_readfirstlane(int(threadIdx.x) >> 6), sg.t1, 0,
+                           int(threadIdx.x) & 63);
   epi.init(src);
   if constexpr (IsEpiXt<Epi>::value) {   // u of the block's rows past the one-piece window
     epi.lu = win + kWinNT;
@@ -943,7 +973,7 @@ __global__ __launch_bounds__(kWinNT, 1) void k_window_pass(WinArgs a, Src src, E
     bool store_win = si == 0;
     if (si > 0) {
       sg = bsegs[si];
-      tl.load(a.tb + int64_t(sg.slice) * (a.ntiles + 1), sg.t0 + wave, sg.t1, 0, lane);   // before the window
+      tl.template load<!kAccum>(win_tb<kAccum>(a, sg.slice), a.ntiles + 1, sg.t0 + wave, sg.t1, 0, lane);   // before the window
       if (sg.flags & kSegLoad) {
         win_fetch<T>(tmp, x, sg.slice, a, rot);
         store_win = true;
@@ -989,6 +1019,22 @@ __global__ __launch_bounds__(kWinNT, 1) void k_window_pass(WinArgs a, Src src, E
     ro[i] = static_cast<unsigned short>(ptr[i + 1] - base);
     if (r % R == 0) tb[int64_t(sl) * (ntiles + 1) + t] = base;
     if (r == rows - 1) tb[int64_t(sl) * (ntiles + 1) + ntiles] = ptr[int64_t(sl) * rows + rows];
+  }
+}
+
+// The row ends of tiles given by their bases and row starts (slices mode; tb
+// as WinArgs::tb, made on the host): one thread per tile, ro of the tile's
+// rows against its base.
+[[maybe_unused]] static __global__ __launch_bounds__(kNT) void k_compact_tiles(int S, int rows, int ntiles,
+                                                       const int* __restrict__ ptr, const int* __restrict__ tb,
+                                                       unsigned short* __restrict__ ro) {
+  const int64_t total = int64_t(S) * ntiles;
+  for (int64_t i = int64_t(blockIdx.x) * kNT + threadIdx.x; i < total; i += int64_t(gridDim.x) * kNT) {
+    const int sl = int(i / ntiles), t = int(i % ntiles);
+    const int* rp = ptr + int64_t(sl) * rows;
+    const int* q = tb + int64_t(sl) * 2 * (ntiles + 1);
+    const int base = q[t], r0 = q[ntiles + 1 + t], r1 = q[ntiles + 2 + t];
+    for (int r = r0; r < r1; ++r) ro[int64_t(sl) * rows + r] = static_cast<unsigned short>(rp[r + 1] - base);
   }
 }
 
