@@ -281,6 +281,15 @@ krcn_status krcn_csr_plan_value_bytes(krcn_csr* h, int* out2_host);
 krcn_status krcn_csr_plan_info(krcn_csr* h, int* out8_host);
 /* Format of each pass's plan (KRCN_PLAN_*): out2_host = {pass 1, pass 2}. */
 krcn_status krcn_csr_plan_format(krcn_csr* h, int* out2_host);
+/* The step a krcn_lanczos call (with this reorth) would run on the handle as
+ * it stands (builds the plans if needed, as krcn_csr_plan_format does):
+ * *step_host = KRCN_LZ_*.  Not collective: a handle of a multi-rank
+ * communicator without plans, or row shards that have not agreed on them,
+ * get the error krcn_lanczos would give. */
+enum { KRCN_LZ_GENERIC = 0, KRCN_LZ_FUSED_WINDOW = 1, KRCN_LZ_FUSED_SORTED = 2, KRCN_LZ_FUSED_SMALL = 3,
+       KRCN_LZ_FUSED_SMALL_XT = 4, KRCN_LZ_TWO_LAUNCH = 5, KRCN_LZ_EARLY = 6, KRCN_LZ_EARLY_COLS = 7,
+       KRCN_LZ_EARLY_ROWS = 8 };
+krcn_status krcn_csr_lanczos_step(krcn_csr* h, int reorth, int* step_host);
 /* Geometry of a dense pass (KRCN_FORMAT_DENSE) over a rows x cols matrix under
  * a lane and a slicing policy (as krcn_csr_set_lanes / krcn_csr_set_slicing
  * take them).  Host arithmetic only: needs no device.

@@ -23,6 +23,15 @@ namespace krcn {
 
 constexpr int kNumCUs = 256;   // MI355X: 8 XCDs x 32 CUs
 constexpr int kNT = 256;           // threads per block for every kernel here
+constexpr int kMaxPartials = 2048;  // upper bound on blocks of a reducing launch
+
+// k_rows_apply (krcn_tiled.hpp): kApplyU rows a thread per round, on
+// apply_grid(rows) blocks.
+constexpr int kApplyU = 4;
+inline int apply_grid(int64_t rows) {
+  int64_t b = (rows + int64_t(kNT) * kApplyU - 1) / (int64_t(kNT) * kApplyU);
+  return int(b < 1 ? 1 : (b > 1024 ? 1024 : b));
+}
 
 // A/B tuning knobs (the variants of DESIGN.md's measurements) are read from
 // the environment only in tuning builds (make variant EXTRA_FLAGS=-DKRCN_TUNING);

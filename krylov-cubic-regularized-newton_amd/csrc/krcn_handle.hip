@@ -219,7 +219,7 @@ extern "C" krcn_status krcn_csr_get_transpose(const krcn_csr* h, int32_t* colptr
 
 // Row shards of a multi-rank communicator pack the pass-1 combine's alpha
 // partials past the d-vector of their one all-reduce per Lanczos step
-// (krcn_lanczos_impl.hpp early_rows).  Each rank's count depends on its own
+// (the early-rows step, krcn_lzstep.hpp).  Each rank's count depends on its own
 // block (the partition balances nonzeros, not rows), so the ranks agree here,
 // after every plan build and before any compute call: the packed length is
 // the maximum over ranks (a rank with fewer zero-fills the rest), and the
@@ -231,7 +231,7 @@ krcn_status agree_rows(krcn_csr* h) {
   const int P = h->comm->nranks, me = h->comm->rank;
   std::vector<double> v(size_t(2 * P), 0.0);
   v[size_t(me)] = pass_partials(h->p1);
-  v[size_t(P + me)] = std::max(h->p1.grid, h->p1.combine_grid) <= kMaxPartials ? 1.0 : 0.0;
+  v[size_t(P + me)] = lz_rows_fit(h->p1.grid, h->p1.combine_grid) ? 1.0 : 0.0;
   DevTmp<double> dv;
   hipStream_t s = nullptr;
   CHK(dv.alloc(v.size() * sizeof(double)));
@@ -387,6 +387,16 @@ extern "C" krcn_status krcn_csr_plan_format(krcn_csr* h, int* out2_host) {
   CHK(ensure_plans(h));
   out2_host[0] = h->p1.kind;
   out2_host[1] = h->p2.kind;
+  return KRCN_OK;
+}
+
+extern "C" krcn_status krcn_csr_lanczos_step(krcn_csr* h, int reorth, int* step_host) {
+  if (!h || !step_host) return fail(KRCN_ERR_INVALID, "krcn_csr_lanczos_step: null argument");
+  CHK(set_device(h));
+  CHK(plans_for_compute(h));
+  const LzStepChoice ch = lanczos_step(lz_step_in(h, reorth));
+  CHK(ch.refusal);
+  *step_host = ch.step;
   return KRCN_OK;
 }
 

@@ -10,13 +10,15 @@
 //   krcn_crn.hip         the device cubic subproblem and the one-call Krylov-CRN step (krcn_cubic.hpp)
 //   krcn_lanczos_f64.hip / krcn_lanczos_f32.hip
 //                        the device Lanczos recurrence (krcn_lanczos_impl.hpp), one dtype each
-// Two host-only headers (plain C++17, no HIP header: they also build with g++
-// under the host sanitizers, tests/native/layout_check.cpp):
+// Three host-only headers (plain C++17, no HIP header: they also build with g++
+// under the host sanitizers, tests/native/layout_check.cpp and lzstep_check.cpp):
 //   krcn_geom.hpp        the constants and small structs host and device agree through (block
 //                        shapes, tile caps, LDS geometry, TileDesc / WinSeg, the lane rule, the
 //                        tuning-knob readers); the kernel headers include it
 //   krcn_layout.hpp      the format policy and one layout function per format, from host row
 //                        pointers to plain structs; krcn_plan.hip materialises them on the device
+//   krcn_lzstep.hpp      which Lanczos step a handle runs, from plain scalars (the recurrence's
+//                        tuning switches live there); krcn_lanczos_impl.hpp enqueues that step
 // This header holds the handle layout, the error macros and the host helpers;
 // it ends by including
 //   krcn_pass.hpp        the pass launcher (run_pass, run_combine, the shape of a pass) that the
@@ -25,6 +27,7 @@
 #include "krcn.h"
 #include "krcn_host.hpp"
 #include "krcn_rendezvous.hpp"
+#include "krcn_lzstep.hpp"
 #include "krcn_kernels.hpp"
 #include "krcn_tiled.hpp"
 #include "krcn_window.hpp"
@@ -295,7 +298,7 @@ struct krcn_csr {
   int sort_nt = 0;            // sorted-tile block size; 0 = by matrix size
   bool plans_ready = false;
   bool p1_unsliced = false;   // pass 2 took a single-window jagged plan: pass 1's sorted tiles go
-                              // unsliced (the two-launch Lanczos step, krcn_lanczos_impl.hpp)
+                              // unsliced (the two-launch Lanczos step, krcn_lzstep.hpp)
   PassPlan p1, p2;            // pass 1 over X, pass 2 over X^T
   // workspace
   double* pa = nullptr;   // partials of reducing launches (pcap entries)

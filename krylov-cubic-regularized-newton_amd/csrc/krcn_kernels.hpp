@@ -25,8 +25,6 @@ namespace krcn {
 
 constexpr int kUnroll = 4;         // elementwise kernels: independent loads per array per thread
 
-constexpr int kMaxPartials = 2048;  // upper bound on blocks of a reducing launch
-
 // Device-resident Lanczos control state (one per matrix handle).
 struct LanczosState {
   int done;        // 1 once |beta| < tol fired (cubic.py:98-99)

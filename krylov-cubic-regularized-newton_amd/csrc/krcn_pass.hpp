@@ -18,6 +18,18 @@ inline void with_lanes(int L, F&& f) {
   }
 }
 
+// 1, 2, 4, 8 or 16 (the CGS2 unrolls, steps and batches, krcn_lanczos_impl.hpp)
+template <typename F>
+inline void with_pow2(int v, F&& f) {
+  switch (v) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 8: f(std::integral_constant<int, 8>{}); break;
+    default: f(std::integral_constant<int, 16>{}); break;
+  }
+}
+
 template <class F>
 inline void with_sort_nt(int nt, F&& f) {
   switch (nt) {
@@ -97,6 +109,31 @@ inline krcn_status run_combine(PassPlan& P, int A, const Src2& rest, const Epi& 
   }
   LAUNCHCHK();
   if (Pout) *Pout = c.grid;
+  return KRCN_OK;
+}
+
+// The pass 2 of a one-piece plan with per-block X^T copies (pass 1's EpiLz1X
+// left the blocks' shares of X^T u in P.xpart): their sum in a fixed order
+// with the epilogue, by k_xt_combine on blocks of rb = 16 / 32 / 64 rows, or
+// (rb = 0) by k_slice_combine.
+template <typename T, class Src2, class Epi>
+inline krcn_status run_xt_combine(PassPlan& P, int rb, const Src2& rest, const Epi& epi, double* partials, int* Pout,
+                                  hipStream_t s) {
+  const int d = int(P.cols);
+  const T* xp = static_cast<const T*>(P.xpart);
+  const int cg = rb ? (d + rb - 1) / rb : combine_grid(d);
+  auto xt = [&](auto rc) {
+    hipLaunchKernelGGL((k_xt_combine<T, Src2, Epi, decltype(rc)::value>), dim3(cg), dim3(kCombineNT), 0, s, d, P.grid,
+                       xp, rest, epi, partials);
+  };
+  if (rb == 16) xt(std::integral_constant<int, 16>{});
+  else if (rb == 64) xt(std::integral_constant<int, 64>{});
+  else if (rb) xt(std::integral_constant<int, 32>{});
+  else
+    hipLaunchKernelGGL((k_slice_combine<T, Src2, Epi>), dim3(cg), dim3(kCombineNT), 0, s, d, P.grid, combine_rows(d),
+                       xp, rest, epi, partials);
+  LAUNCHCHK();
+  *Pout = cg;
   return KRCN_OK;
 }
 
@@ -257,8 +294,7 @@ inline krcn_status run_pass(PassPlan& P, const Src& first, const Src2& rest, con
   }
   if (kind == KRCN_PLAN_DENSE) {
     // dense plans run the generic step only: the sources of the fused steps
-    // are never selected for one (lanczos_impl: fuse, fuse_u and early need a
-    // window, sorted or jagged pass 1)
+    // are never selected for one (krcn_lzstep.hpp lanczos_step)
     if (z || u) return fail(KRCN_ERR_UNSUPPORTED, "fused Lanczos steps do not run over a dense plan");
   }
   // the stored width of the plan's values: the arithmetic's, or fp32 under
@@ -284,8 +320,8 @@ inline krcn_status run_pass(PassPlan& P, const Src& first, const Src2& rest, con
   }
   // partial arrays the combine sums (a fused step B over sorted tiles always
   // ends in it, whatever S is: only EpiWeighted runs in the main launch.
-  // lanczos_impl takes that step for sliced plans only, fuse_sorted: an
-  // unsliced plan owns no P.part)
+  // krcn_lzstep.hpp lanczos_step takes that step for sliced plans only,
+  // fused-sorted: an unsliced plan owns no P.part)
   const int A = z && !weighted && kind == KRCN_PLAN_SORTED ? P.S : combine_arrays(P);
   // a reducing launch writes one partial per block, the combine's when one
   // follows: the buffer must hold them.  This is the grid run_combine will
@@ -339,6 +375,25 @@ inline krcn_status run_pass(PassPlan& P, const Src& first, const Src2& rest, con
   }
   if (Pout) *Pout = P.grid;
   return KRCN_OK;
+}
+
+// What lanczos_step (krcn_lzstep.hpp) reads of a handle as it stands: the
+// recurrence and krcn_csr_lanczos_step both choose the step from this.
+inline LzStepIn lz_step_in(const krcn_csr* h, int reorth) {
+  LzStepIn in;
+  in.shard = h->shard;
+  in.multi = h->comm && h->comm->nranks > 1;
+  in.f64 = h->dtype == KRCN_F64;
+  in.reorth = reorth != 0;
+  in.n = h->n, in.d = h->d, in.pcap = h->pcap;
+  in.p1_kind = h->p1.kind, in.p1_S = h->p1.S, in.p1_grid = h->p1.grid, in.p1_combine_grid = h->p1.combine_grid;
+  in.p1_xt = h->p1.xt;
+  in.p2_kind = h->p2.kind, in.p2_S = h->p2.S, in.p2_jG = h->p2.jG;
+  in.pq = h->pq != nullptr;
+  in.pq_local = pass_partials(h->p1);
+  in.rows_pq = h->rows_pq, in.rows_early = h->rows_early;
+  in.knobs = lz_knobs();
+  return in;
 }
 
 #if KRCN_FOLD

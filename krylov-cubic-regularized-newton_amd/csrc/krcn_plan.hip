@@ -697,9 +697,8 @@ krcn_status ensure_plans(krcn_csr* h) {
   // 1's slicing.  Off by default: unslicing rcv1's sorted pass 1 for the
   // two-launch step ran 33.4-34.1 k HVP/s against 43.3-44.2 k for the sliced
   // pass + combine (pass 1 16 against 10 us, pass 2 13.7 against 10.3 us;
-  // profiles/r04_rcv1_lz2.txt).  A/B knob KRCN_LZ2=1 turns it on.  (The
-  // step itself reads the same knob as on unless 0, krcn_lanczos_impl.hpp
-  // lanczos_impl fuse_u: it runs wherever a plan allows it.)
+  // profiles/r04_rcv1_lz2.txt).  A/B knob KRCN_LZ2=1 turns it on (the step
+  // itself reads the same knob the other way round: krcn_lzstep.hpp LzKnobs::lz2).
   static const bool lz2_env = tuning_off("KRCN_LZ2");
   krcn_status r = h->dtype == KRCN_F64 ? build_plans<double>(h, lz2_env, s) : build_plans<float>(h, lz2_env, s);
   (void)hipStreamDestroy(s);

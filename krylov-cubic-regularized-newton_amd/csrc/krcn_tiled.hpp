@@ -784,12 +784,7 @@ __global__ __launch_bounds__(NT) void k_slice_combine_small(int rows, int S, con
 // first row is applied (round 5: one row at a time left the synth row apply a
 // chain of dependent round trips, 1 M rows on 1,024 blocks).  Its grid:
 // apply_grid(rows) blocks, each with rows to apply (every block runs the
-// source prologue and writes one partial).
-constexpr int kApplyU = 4;
-__host__ inline int apply_grid(int64_t rows) {
-  int64_t b = (rows + int64_t(kNT) * kApplyU - 1) / (int64_t(kNT) * kApplyU);
-  return int(b < 1 ? 1 : (b > 1024 ? 1024 : b));
-}
+// source prologue and writes one partial; krcn_geom.hpp, with kApplyU).
 template <typename T, class Src, class Epi>
 __global__ __launch_bounds__(kNT) void k_rows_apply(int rows, const T* __restrict__ sums, Src src, Epi epi,
                                                     double* __restrict__ partials) {

@@ -85,6 +85,7 @@ SIGNATURES = {
     "krcn_csr_placement_info": [_vp, _dp],
     "krcn_csr_plan_info": [_vp, ctypes.POINTER(ctypes.c_int)],
     "krcn_csr_plan_format": [_vp, ctypes.POINTER(ctypes.c_int)],
+    "krcn_csr_lanczos_step": [_vp, _i, ctypes.POINTER(ctypes.c_int)],
     "krcn_dense_geometry": [_i64, _i64, _i, _i, _i, ctypes.POINTER(_i64)],
     "krcn_csr_get_transpose": [_vp, _vp, _vp, _vp, _vp],
     "krcn_csr_attach_comm": [_vp, _vp],

@@ -191,6 +191,17 @@ class DeviceCSR:
         call("krcn_csr_plan_format", self._h, buf)
         return {"pass1": self._FORMAT_NAMES[buf[0]], "pass2": self._FORMAT_NAMES[buf[1]]}
 
+    _STEP_NAMES = ("generic", "fused-window", "fused-sorted", "fused-small", "fused-small-xt", "two-launch",
+                   "early", "early-cols", "early-rows")
+
+    def lanczos_step(self, reorth=False):
+        """The step a lanczos(.., reorth=reorth) call would run on the handle as it stands
+        (krcn_csr_lanczos_step): generic, fused-window, fused-sorted, fused-small, fused-small-xt,
+        two-launch, early, early-cols or early-rows.  Not collective."""
+        step = ctypes.c_int(-1)
+        call("krcn_csr_lanczos_step", self._h, int(bool(reorth)), ctypes.byref(step))
+        return self._STEP_NAMES[step.value]
+
     def attach_comm(self, comm):
         call("krcn_csr_attach_comm", self._h, comm.handle if comm is not None else None)
         self._comm = comm

@@ -98,33 +98,44 @@ def test_lanczos_breakdown_quirks(f2, r, ms):
 #  two_launch: unsliced sorted pass 1 (z_j formed in the gathers, u' = w X z_j
 #          stored) + single-window jagged pass 2 whose blocks settle beta and
 #          scale their window (SrcLzU): two launches a step, no combine.
+#  fused_win: window-slices pass 1 (z_j formed in the windows, the slice
+#          combine settles beta, pass 2 re-forms z_j: EpiLz2::zw) beside a
+#          sorted pass 2, which cannot reduce the early step's two sums.  The
+#          operator is padded to D_PAD columns (below) for the sliced window.
 FUSED_PLANS = {"sorted": dict(slicing=8, fmt=krcn.KRCN_FORMAT_SORTED),
                "small": dict(fmt=krcn.KRCN_FORMAT_WINDOW),
-               "two_launch": dict(pass_formats=(krcn.KRCN_FORMAT_SORTED, krcn.KRCN_FORMAT_JAG))}
+               "two_launch": dict(pass_formats=(krcn.KRCN_FORMAT_SORTED, krcn.KRCN_FORMAT_JAG)),
+               "fused_win": dict(pass_formats=(krcn.KRCN_FORMAT_WINDOW, krcn.KRCN_FORMAT_SORTED))}
 
 
-def check_fused_plan(X, kind):
-    info, fmt = X.plan_info(), X.plan_format()
+def fused_operator(A0, b, x0, kind):
+    """The operator on the plans of `kind`, which must take the step the kind is named for."""
+    if kind == "fused_win":
+        A0, x0 = pad_cols(A0, D_PAD), np.concatenate([x0, np.zeros(D_PAD - A0.shape[1])])
+    X, w, g = device_operator(A0, b, x0, **FUSED_PLANS[kind])
+    info, fmt, step = X.plan_info(), X.plan_format(), X.lanczos_step()
     if kind == "sorted":
-        assert info["pass1"][0] == -8
+        assert info["pass1"][0] == -8 and step == "fused-sorted"
     elif kind == "two_launch":
-        assert info["pass1"][0] == -1 and fmt["pass2"] == "jagged" and info["pass2"][0] == 1
+        assert info["pass1"][0] == -1 and fmt["pass2"] == "jagged" and info["pass2"][0] == 1 and step == "two-launch"
+    elif kind == "fused_win":
+        assert fmt == {"pass1": "window-slices", "pass2": "sorted"} and step == "fused-window"
     else:
         assert fmt["pass1"] == "window-accum" and info["pass1"][0] == 1 and X.d <= 1024
+        assert step == "fused-small-xt"   # (these plans hold the per-block X^T copies)
+    return X, w, g
 
 
 @pytest.mark.parametrize("kind", sorted(FUSED_PLANS))
 @pytest.mark.parametrize("m", [1, 10])
 def test_lanczos_fused_step_b_vs_golden(f1, f2, m, kind):
     A = golden_csr(f1)
-    X, w, g = device_operator(A, f1["b"], f1["x0"], **FUSED_PLANS[kind])
-    check_fused_plan(X, kind)
+    X, w, g = fused_operator(A, f1["b"], f1["x0"], kind)
     V, al, be, info = X.lanczos(w, g, m)
     assert info.m_eff == m and not info.breakdown and info.hvps == m
     assert rel_err(al, f2[f"alphas_m{m}"]) < 1e-11
     assert rel_err(be, f2[f"betas_m{m}"]) < 1e-11
-    Vh = V.cpu().numpy()[:info.m_eff].T
-    assert np.abs(Vh - f2[f"V_m{m}"]).max() < 1e-6
+    check_padded_basis(V, info.m_eff, f2[f"V_m{m}"], 1e-6)
     assert abs(info.beta_last - float(f2[f"beta_m{m}"])) <= 1e-11 * max(1e-300, abs(float(f2[f"beta_m{m}"])))
     assert abs(info.gnorm - np.linalg.norm(f2["g"])) <= 1e-13 * np.linalg.norm(f2["g"])
 
@@ -133,8 +144,7 @@ def test_lanczos_fused_step_b_vs_golden(f1, f2, m, kind):
 @pytest.mark.parametrize("r,ms", [(1, (2, 3, 5)), (3, (4, 5, 10))])
 def test_lanczos_fused_step_b_breakdown_quirks(f2, r, ms, kind):
     A = golden_csr(f2, f"r{r}_")
-    X, w, g = device_operator(A, f2[f"r{r}_b"], np.full(A.shape[1], 0.5), **FUSED_PLANS[kind])
-    check_fused_plan(X, kind)
+    X, w, g = fused_operator(A, f2[f"r{r}_b"], np.full(A.shape[1], 0.5), kind)
     for m in ms:
         key = f"r{r}_m{m}"
         V, al, be, info = X.lanczos(w, g, m)
@@ -143,8 +153,7 @@ def test_lanczos_fused_step_b_breakdown_quirks(f2, r, ms, kind):
         assert info.m_eff == Vref.shape[1]
         assert rel_err(al, f2[f"{key}_alphas"]) < 1e-11
         np.testing.assert_allclose(be, f2[f"{key}_betas"], rtol=1e-11, atol=0)
-        Vh = V.cpu().numpy()[:info.m_eff].T
-        assert np.abs(Vh - Vref).max() < 1e-12
+        Vh = check_padded_basis(V, info.m_eff, Vref, 1e-12)
         if m == r + 1:
             assert np.all(Vh[:, -1] == 0) and be[-1] == 0
         assert info.beta_last < 1e-6
@@ -182,6 +191,7 @@ def early_operator(A0, b, x0, kind):
     else:
         assert fmt["pass1"] == "window-slices"
         assert fmt["pass2"] == ("jagged" if kind == "early_jag" else "window-accum")
+    assert X.lanczos_step() == "early"
     return X, w, g
 
 
@@ -315,6 +325,7 @@ def test_lanczos_reorth_matches_cgs2_oracle(f1):
     wh = O.hessian_weights(A, x)
     gh = g.cpu().numpy()
     _, al_ref, be_ref, _ = O.lanczos_cgs2(lambda v: O.hvp_from_weights(A, wh, v), gh, 40)
+    assert X.lanczos_step(reorth=True) == "generic"
     V, al, be, info = X.lanczos(w, g, 40, reorth=True)
     assert info.m_eff == len(al_ref)
     assert rel_err(al, al_ref) < 1e-10
@@ -358,6 +369,7 @@ def test_reorth_rcv1_fp64_and_orthogonality(m):
     X, w, g = device_operator(A, b, x)
     wh = O.hessian_weights(A, x)
     _, al_r, be_r, _ = O.lanczos_cgs2(lambda v: O.hvp_from_weights(A, wh, v), g.cpu().numpy(), m)
+    assert X.lanczos_step(reorth=True) == "generic"
     V, al, be, info = X.lanczos(w, g, m, reorth=True)
     assert info.m_eff == m
     assert rel_err(al, al_r) < 1e-10
@@ -379,6 +391,7 @@ def test_reorth_wide_rows_fp64():
     X, w, g = device_operator(A, b, x)
     m = 260
     X.reserve(m, reorth=True)
+    assert X.lanczos_step(reorth=True) == "generic"
     V, al, be, info = X.lanczos(w, g, m, reorth=True)
     assert info.m_eff == m
     wh = O.hessian_weights(A, x)
@@ -406,6 +419,7 @@ def test_reorth_breakdown_matches_cgs2_oracle(d, dtype):
     wh = O.hessian_weights(A, x)
     gh = O.gradient(A, O.labels01(b), x)
     Vr, al_r, be_r, _ = O.lanczos_cgs2(lambda v: O.hvp_from_weights(A, wh, v), gh, 40)
+    assert X.lanczos_step(reorth=True) == "generic"
     V, al, be, info = X.lanczos(w, g, 40, reorth=True)
     assert info.m_eff == len(al_r) < 40
     tol = 1e-9 if dtype == torch.float64 else 1e-3
@@ -425,6 +439,7 @@ def test_reorth_fp32_stress_config():
     w = X.weights(Ax)
     g = X.gradient(Ax, torch.from_numpy(O.labels01(b)).to(DEV, torch.float32))
     m = 120
+    assert X.lanczos_step(reorth=True) == "generic"
     V, al, be, info = X.lanczos(w, g, m, reorth=True)
     assert info.m_eff == m
     wh = O.hessian_weights(A, x)

@@ -83,6 +83,7 @@ def test_shard_modes_lanczos_l2(f1, comm, mode, m):
     Ax = X.matvec(x)
     w = X.weights(Ax)
     g = X.gradient(Ax, t(O.labels01(f1["b"])))
+    assert X.lanczos_step() == ("early-rows" if mode == _lib.KRCN_SHARD_ROWS else "early-cols")
     V, al, be, info = X.lanczos(w, g, m, l2=0.01)
     wh = O.hessian_weights(A, f1["x0"])
     Vr, al_r, be_r, beta_r = O.lanczos(lambda v: O.hvp_from_weights(A, wh, v, l2=0.01), g.cpu().numpy(), m)

@@ -50,14 +50,16 @@ def rank_statistics(vs, m):
         y = X.hvp(w, (g / gn).contiguous())
         _, al, be, info = X.lanczos(w, g, m)
         return {"value": val, "g": g.cpu().numpy(), "gn": gn, "y": y.cpu().numpy(), "al": al, "be": be,
-                "m_eff": info.m_eff, "beta": info.beta_last, "fmt": X.plan_format(), "plan": X.plan_info()}
+                "m_eff": info.m_eff, "beta": info.beta_last, "fmt": X.plan_format(), "plan": X.plan_info(),
+                "step": X.lanczos_step()}
 
     return vs.run(fn)
 
 
-def check(f, res, g, y, lanczos_tol):
+def check(f, res, g, y, lanczos_tol, step):
     st = int(f["stride"])
     for r in res:
+        assert r["step"] == step   # on every rank
         assert abs(r["value"] - f["value"]) <= 1e-13 * abs(f["value"])
         assert abs(r["gn"] - f["g_norm"]) <= 1e-13 * f["g_norm"]
         assert r["m_eff"] == len(f["alphas"])
@@ -85,7 +87,7 @@ def test_news20_cols_x8():
     g = np.concatenate([r["g"] for r in res])
     y = np.concatenate([r["y"] for r in res])
     assert g.shape[0] == A.shape[1]
-    check(f, res, g, y, 1e-7)
+    check(f, res, g, y, 1e-7, "early-cols")
 
 
 @pytest.fixture(scope="module")
@@ -109,7 +111,7 @@ def test_synth_rows_x8(synth_problem):
     # a rank's X block gathers the whole d-vector: the auto policy runs its
     # pass 1 in jagged slice groups
     assert res[0]["fmt"]["pass1"] == "jagged"
-    check(f, res, res[0]["g"], res[0]["y"], 1e-11)
+    check(f, res, res[0]["g"], res[0]["y"], 1e-11, "early-rows")
 
 
 def test_synth_rows_x8_crn_step(synth_problem):
@@ -185,7 +187,7 @@ def test_rows_x2_unequal_blocks_agree():
             Ax = X.matvec(x)
             g = X.gradient(Ax, vs.b[r])
             _, al, be, info = X.lanczos(X.weights(Ax), g, m)
-            return al, be, info.m_eff, X.plan_info(), g.cpu().numpy()
+            return al, be, info.m_eff, X.plan_info(), X.lanczos_step()
 
         res = vs.run(fn)
     finally:
@@ -194,8 +196,8 @@ def test_rows_x2_unequal_blocks_agree():
     x = np.full(A.shape[1], 0.5)
     wh = O.hessian_weights(A, x)
     _, al_r, be_r, _ = O.lanczos(lambda v: O.hvp_from_weights(A, wh, v), O.gradient(A, O.labels01(b), x), m)
-    for al, be, m_eff, _, _ in res:
-        assert m_eff == m
+    for al, be, m_eff, _, step in res:
+        assert m_eff == m and step == "early-rows"
         assert rel_err(al, al_r) < 1e-11
         assert rel_err(be, be_r) < 1e-11
         np.testing.assert_array_equal(al, res[0][0])

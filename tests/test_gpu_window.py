@@ -261,7 +261,7 @@ def test_one_piece_fused_xt_lanczos(case):
         A.sort_indices()
         d = A.shape[1]
     X = krcn.DeviceCSR(A, fmt=krcn.KRCN_FORMAT_AUTO if case == "w8a-like" else krcn.KRCN_FORMAT_WINDOW)
-    assert X.plan_format()["pass1"] == "window-accum"
+    assert X.plan_format()["pass1"] == "window-accum" and X.lanczos_step() == "fused-small-xt"
     x = np.random.default_rng(5).uniform(-0.2, 0.2, size=d)
     w = O.hessian_weights(A, x)
     g = X.gradient(X.matvec(t(x)), t(O.labels01(b)))
@@ -289,7 +289,7 @@ def test_one_piece_fused_xt_lanczos(case):
 def test_one_piece_fused_xt_lanczos_fp32():
     A, b = _xt_problem(50_000, 300, 580_000, seed=77)
     X = krcn.DeviceCSR(A, dtype=torch.float32)
-    assert X.plan_format()["pass1"] == "window-accum"
+    assert X.plan_format()["pass1"] == "window-accum" and X.lanczos_step() == "fused-small-xt"
     x = np.random.default_rng(6).uniform(-0.2, 0.2, size=A.shape[1])
     w = O.hessian_weights(A, x)
     g = X.gradient(X.matvec(t(x, torch.float32)), t(O.labels01(b), torch.float32))

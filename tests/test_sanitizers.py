@@ -14,7 +14,9 @@ build, with g++ and AddressSanitizer + UBSan or ThreadSanitizer:
   * layout_asan: the pass-plan layouts (csrc/krcn_layout.hpp) behind
     tests/native/layout_check.cpp, which checks every layout's invariants on
     small patterns at the boundaries of the layout rules (ASan + UBSan only:
-    the layouts are single-threaded).
+    the layouts are single-threaded);
+  * lzstep_asan: the Lanczos step choice (csrc/krcn_lzstep.hpp) behind
+    tests/native/lzstep_check.cpp; tests/test_lanczos_step.py runs it.
 A sanitizer finding aborts the program (-fno-sanitize-recover), so every
 check here is also "no report".
 """
