@@ -31,7 +31,15 @@
  *     result, cap (12 + 8 cap) device bytes for k_cap = k rounded up to a
  *     multiple of 64, counted by krcn_csr_owned_bytes and freed by
  *     krcn_csr_destroy, plus pinned host memory (the result's mirror and the
- *     staging ring).  A handle of a multi-rank communicator never builds
+ *     staging ring).  The block calls (krcn_matvec_block, krcn_rmatvec_block,
+ *     krcn_hvp_block) build no plans.  krcn_hvp_block allocates its (n, k)
+ *     intermediate, n * k * sizeof(dtype) device bytes, at its first call and
+ *     again when k grows; the first block call that walks X, and the first
+ *     that walks X^T, copies that matrix's row pointers to the host once
+ *     (synchronising the stream) and keeps the ids of its rows above
+ *     KRCN_BLOCK_LONG_ROW on the device, 4 bytes each, nothing when there is
+ *     none.  Both are counted by krcn_csr_owned_bytes and freed by
+ *     krcn_csr_destroy.  A handle of a multi-rank communicator never builds
  *     or allocates inside a compute call (that call fails instead), so no
  *     rank synchronises the device while its peers wait in a collective.
  *   - Errors: every call returns a krcn_status (0 = OK).  The message of the
@@ -433,6 +441,42 @@ krcn_status krcn_coord_update(krcn_csr* h, int k, const int32_t* cols_host, cons
  * (update); tests use small values to cross window boundaries on small n.
  * Results of the update do not depend on it. */
 krcn_status krcn_csr_set_coord_window(krcn_csr* h, int rows);
+
+/* ---- block products: k vectors per pass over X ----------------------------- */
+/* A block of k vectors over a space of length L (n or d) is an (L, k) row-major
+ * DEVICE array of the handle's dtype: element (i, j) at i * k + j, a
+ * C-contiguous (L, k) torch or numpy array; 1 <= k <= KRCN_BLOCK_MAX, any k.
+ * Each call streams the matrix (index + value) once for the whole block and
+ * gathers the k contiguous values of a column of the block together; pass 1
+ * walks the caller's CSR of X, pass 2 the handle's transposed CSR.  The calls
+ * need no pass plans (they never trigger the plan build) and do not use the
+ * handle's scratch vectors.  Unsharded handles only (a sharded handle gets
+ * KRCN_ERR_UNSUPPORTED); a null handle, a k outside the range, a w_cols that is
+ * neither 1 nor k or a null array are KRCN_ERR_INVALID, all before any HIP call.
+ * Inputs and outputs must not alias one another.
+ * Summation order: entry (r, j) is the left-to-right sum over row r's stored
+ * elements of a_e * V[col_e, j], product and sum rounded separately: scipy's
+ * csr_matvecs order on X and csc_matvecs order on X^T, bit for bit in fp64,
+ * for every row of at most KRCN_BLOCK_LONG_ROW stored elements.  A longer row
+ * (of X or of X^T) is cut into 1024 / K contiguous segments of
+ * ceil(len / (1024 / K)) elements, K the next power of two >= k; each segment is
+ * summed left to right and the segment sums are added in segment order: a
+ * fixed order that depends on the row's length and K alone (no atomics;
+ * bitwise equal from run to run and whatever the other rows are).
+ * n == 0 or nnz == 0: zeros, and l2_j V[:, j] from krcn_hvp_block, without
+ * reading the matrix. */
+enum { KRCN_BLOCK_MAX = 16, KRCN_BLOCK_LONG_ROW = 512 };
+/* T (n,k) = X V (d,k).                      k single krcn_matvec calls */
+krcn_status krcn_matvec_block(krcn_csr* h, int k, const void* V, void* T, void* stream);
+/* Y (d,k) = X^T U (n,k) / n_global.         k single krcn_rmatvec calls */
+krcn_status krcn_rmatvec_block(krcn_csr* h, int k, const void* U, void* Y, void* stream);
+/* Y[:,j] = X^T (w_j (.) X V[:,j]) / n + l2_j V[:,j].  w_cols = 1: one n-vector
+ * of weights for every column (H V at one x); w_cols = k: an (n,k) block
+ * (k problems over one X).  l2_host: k HOST doubles, read before the call
+ * returns; NULL = all zero.  A column with l2_j == 0 never reads V in the
+ * epilogue, as krcn_hvp.  Replaces hess_vec_prod, loss.py:289-302, k times. */
+krcn_status krcn_hvp_block(krcn_csr* h, int k, const void* w, int w_cols, const void* V, void* Y,
+                           const double* l2_host, void* stream);
 
 /* ---- Lanczos (optimizer/cubic.py:77-111) -------------------------------- */
 /* SYNCHRONOUS on return of alphas/betas/info.  Runs the reference three-term

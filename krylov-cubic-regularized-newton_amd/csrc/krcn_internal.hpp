@@ -7,6 +7,7 @@
 //   krcn_comm.hip        the RCCL communicator and the virtual communicator
 //   krcn_ops.hip         objective pieces (Ax, X^T u, weights, HVP, gradient, loss, dots)
 //   krcn_coord.hip       coordinate blocks of SSCN (gradient, Hessian block, Ax update)
+//   krcn_block.hip       block products: k vectors per pass over the matrix (X V, X^T U / n, the block HVP)
 //   krcn_crn.hip         the device cubic subproblem and the one-call Krylov-CRN step (krcn_cubic.hpp)
 //   krcn_lanczos_f64.hip / krcn_lanczos_f32.hip
 //                        the device Lanczos recurrence (krcn_lanczos_impl.hpp), one dtype each
@@ -336,6 +337,11 @@ struct krcn_csr {
   double* crn_res_dev = nullptr;
   CoordWs* cw = nullptr;      // coordinate workspace (first krcn_coord_* call; its device block is in own)
   int coord_window = 0;       // krcn_csr_set_coord_window (0: auto)
+  void* blk_u = nullptr;      // krcn_hvp_block: its (n, blk_k) intermediate (krcn_block.hip; grown when k grows)
+  int blk_k = 0;
+  int* blk_long[2] = {};      // block products: rows of X / X^T above KRCN_BLOCK_LONG_ROW, listed at the
+  int blk_nlong[2] = {};      //   first pass over that matrix (null while there is none)
+  bool blk_listed[2] = {};
   DevOwner own;               // every device buffer above but betas_dev (it aliases alphas_dev)
   krcn_comm* comm = nullptr;
   bool prof = false;

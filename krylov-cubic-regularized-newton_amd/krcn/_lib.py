@@ -29,6 +29,7 @@ KRCN_PLAN_WAVE, KRCN_PLAN_SORTED, KRCN_PLAN_WINDOW_SLICES, KRCN_PLAN_WINDOW_ACCU
 KRCN_PLAN_JAG, KRCN_PLAN_DENSE = 5, 6
 KRCN_SPACE_N, KRCN_SPACE_D = 0, 1
 KRCN_COORD_MAX = 1024
+KRCN_BLOCK_MAX, KRCN_BLOCK_LONG_ROW = 16, 512
 
 _STATUS_NAMES = {1: "KRCN_ERR_INVALID", 2: "KRCN_ERR_HIP", 3: "KRCN_ERR_RCCL",
                  4: "KRCN_ERR_UNSUPPORTED"}
@@ -101,6 +102,9 @@ SIGNATURES = {
     "krcn_coord_hessian": [_vp, _i, _vp, _vp, _d, _dp, _vp],
     "krcn_coord_update": [_vp, _i, _vp, _dp, _vp, _vp, _vp],
     "krcn_csr_set_coord_window": [_vp, _i],
+    "krcn_matvec_block": [_vp, _i, _vp, _vp, _vp],
+    "krcn_rmatvec_block": [_vp, _i, _vp, _vp, _vp],
+    "krcn_hvp_block": [_vp, _i, _vp, _i, _vp, _vp, _dp, _vp],
     "krcn_lanczos": [_vp, _vp, _vp, _i, _i, _d, _d, _vp, _dp, _dp,
                      ctypes.POINTER(LanczosInfo), _vp],
     "krcn_basis_combine": [_vp, _i, _vp, _dp, _vp, _vp, _vp],

@@ -344,6 +344,58 @@ class DeviceCSR:
              _stream(self.device))
         return out
 
+    # -- block products: k vectors per pass over X ---------------------------
+    def _check_block(self, t, rows, k, name):
+        if not isinstance(t, torch.Tensor) or t.device != self.device:
+            raise TypeError(f"{name} must be a torch tensor on {self.device}")
+        if t.dtype != self.dtype:
+            raise TypeError(f"{name} must have dtype {self.dtype}, got {t.dtype}")
+        if t.dim() != 2 or t.shape[0] != rows or (k is not None and t.shape[1] != k) or not t.is_contiguous():
+            want = f"({rows}, {'k' if k is None else k})"
+            raise ValueError(f"{name} must be a contiguous {want} tensor, got shape {tuple(t.shape)}")
+        return t
+
+    def _block_out(self, out, rows, k):
+        if out is None:
+            return torch.empty((rows, k), dtype=self.dtype, device=self.device)
+        return self._check_block(out, rows, k, "out")
+
+    def matvec_block(self, V, out=None):
+        """T (n, k) = X V for a (d, k) block, 1 <= k <= KRCN_BLOCK_MAX: one pass over X
+        (krcn_matvec_block; scipy's csr_matvecs order).  out must not alias V."""
+        k = int(self._check_block(V, self.d, None, "V").shape[1])
+        out = self._block_out(out, self.n, k)
+        call("krcn_matvec_block", self._h, k, _ptr(V), _ptr(out), _stream(self.device))
+        return out
+
+    def rmatvec_block(self, U, out=None):
+        """Y (d, k) = X^T U / n_global for an (n, k) block (krcn_rmatvec_block)."""
+        k = int(self._check_block(U, self.n, None, "U").shape[1])
+        out = self._block_out(out, self.d, k)
+        call("krcn_rmatvec_block", self._h, k, _ptr(U), _ptr(out), _stream(self.device))
+        return out
+
+    def hvp_block(self, w, V, l2=0.0, out=None):
+        """Y[:, j] = X^T (w_j * X V[:, j]) / n + l2_j V[:, j] for a (d, k) block in two
+        passes over the matrix (krcn_hvp_block).  w: (n,) weights shared by every
+        column, or an (n, k) block; l2: a float or a length-k sequence."""
+        k = int(self._check_block(V, self.d, None, "V").shape[1])
+        if isinstance(w, torch.Tensor) and w.dim() == 2:
+            w_cols = int(self._check_block(w, self.n, None, "w").shape[1])
+        else:
+            self._check(w, self.n, "w")
+            w_cols = 1
+        if np.ndim(l2) == 0:
+            l2s = np.full(max(k, 1), float(l2), dtype=np.float64)
+        else:
+            l2s = np.ascontiguousarray(np.asarray(l2, dtype=np.float64).reshape(-1))
+            if len(l2s) != k:
+                raise ValueError(f"l2 must be a float or have one entry per column ({k}), got {len(l2s)}")
+        out = self._block_out(out, self.d, k)
+        call("krcn_hvp_block", self._h, k, _ptr(w), w_cols, _ptr(V), _ptr(out), l2s.ctypes.data_as(_lib._dp),
+             _stream(self.device))
+        return out
+
     # -- Lanczos -----------------------------------------------------------
     def lanczos(self, w, g, m, reorth=False, tol=1e-6, l2=0.0, V=None):
         """Three-term Lanczos on v -> hvp(w, v) from g (cubic.py:77-111).

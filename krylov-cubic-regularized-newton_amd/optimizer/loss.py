@@ -382,6 +382,25 @@ class LogisticRegression(Oracle):
         y = self.device_matrix.hvp(w, self.to_device(v), l2=float(self.l2))
         return y if isinstance(v, torch.Tensor) else self.to_host(y)
 
+    def hess_mat_prod(self, x, V):
+        """H(x) V for a (d, k') block V of any k' >= 1: the block HVP
+        (krcn_hvp_block) over blocks of at most KRCN_BLOCK_MAX columns, two
+        passes over the matrix per block instead of two per column, with the
+        weights hoisted once.  numpy in -> numpy out, torch in -> device tensor."""
+        self._no_shards("hess_mat_prod")
+        is_torch = isinstance(V, torch.Tensor)
+        if V.ndim != 2 or V.shape[0] != self.dim or V.shape[1] < 1:
+            raise ValueError(f"V must be a ({self.dim}, k) block with k >= 1, got shape {tuple(V.shape)}")
+        w = self._weights_for(x)
+        X = self.device_matrix
+        Vd = V.to(device=self.device, dtype=self.dtype) if is_torch else \
+            torch.from_numpy(np.ascontiguousarray(V, dtype=self._np_dtype())).to(self.device)
+        out = torch.empty((self.dim, Vd.shape[1]), dtype=self.dtype, device=self.device)
+        for c0 in range(0, Vd.shape[1], _lib.KRCN_BLOCK_MAX):
+            c1 = min(c0 + _lib.KRCN_BLOCK_MAX, Vd.shape[1])
+            out[:, c0:c1] = X.hvp_block(w, Vd[:, c0:c1].contiguous(), l2=float(self.l2))
+        return out if is_torch else self.to_host(out)
+
     def hess_operator(self, x):
         return HessianOperator(self, x)
 
@@ -404,16 +423,37 @@ class LogisticRegression(Oracle):
         if self.shard is not None:
             raise NotImplementedError(f"{what} is implemented for unsharded problems")
 
-    def hessian(self, x):
+    def hessian(self, x, block=None):
         """Dense Hessian X^T diag(w) X / n + l2 I (loss.py:249-255): the
         coordinate-block kernel over all columns for d <= KRCN_COORD_MAX, one
         device HVP per column above that; numpy (d, d), for the full-space CRN
-        at small d."""
+        at small d.  block=k (1..KRCN_BLOCK_MAX) builds the d > KRCN_COORD_MAX
+        Hessian from block HVPs over k unit vectors at a time instead: d / k
+        matrix reads, not d (the sums of a long row then run in the block
+        kernels' order, so entries may differ from block=None in the last bits)."""
         self._no_shards("the dense / coordinate Hessian")
+        if block is not None and not 1 <= int(block) <= _lib.KRCN_BLOCK_MAX:
+            raise ValueError(f"block must be None or 1..{_lib.KRCN_BLOCK_MAX}, got {block!r}")
         if self.dim <= _lib.KRCN_COORD_MAX:
             return self.device_matrix.coord_hessian(np.arange(self.dim), self._device_Ax(x), float(self.l2))
+        if block is not None:
+            return self._hessian_by_blocks(x, int(block))
         cols = self._unit_columns(x, range(self.dim))
         return torch.stack(cols, dim=1).cpu().numpy().astype(np.float64)
+
+    def _hessian_by_blocks(self, x, k):
+        w = self._weights_for(x)
+        X = self.device_matrix
+        H = torch.empty((self.dim, self.dim), dtype=self.dtype, device=self.device)
+        E = torch.zeros((self.dim, k), dtype=self.dtype, device=self.device)
+        for c0 in range(0, self.dim, k):
+            kc = min(k, self.dim - c0)
+            Ec = E if kc == k else torch.zeros((self.dim, kc), dtype=self.dtype, device=self.device)
+            diag = torch.arange(kc, device=self.device)
+            Ec[c0 + diag, diag] = 1.0
+            H[:, c0:c0 + kc] = X.hvp_block(w, Ec, l2=float(self.l2))
+            Ec[c0 + diag, diag] = 0.0
+        return H.cpu().numpy().astype(np.float64)
 
     def partial_gradient(self, x, I):
         """Coordinates I of the gradient (loss.py:234-247) by the coordinate
