@@ -325,6 +325,16 @@ krcn_status krcn_csr_set_graph(krcn_csr* h, int on);
  * the default), 0 off, 1..8 forced.  Invalidates the plans.  Replaces no
  * reference call (scipy's arrays live in host memory, optimizer/loss.py:188). */
 krcn_status krcn_csr_set_placement_trials(krcn_csr* h, int trials);
+/* Which of the probed placements is kept: keep = -1 the fastest (the default),
+ * 0..7 placement min(keep, probed - 1) whatever the timings say, both at the
+ * plan-build probe and after the search over krcn_lanczos calls below.  Every
+ * placement is still built and timed.  Pins a placement for A/B timing, and
+ * lets a test move the buffers on every run instead of when the timer says so.
+ * A change invalidates the plans; a value outside -1..7 is KRCN_ERR_INVALID.
+ * krcn_csr_get_placement_keep reads it back (the 24 doubles of
+ * krcn_csr_placement_info are all taken).  Replaces no reference call. */
+krcn_status krcn_csr_set_placement_keep(krcn_csr* h, int keep);
+krcn_status krcn_csr_get_placement_keep(const krcn_csr* h, int* keep_host);
 /* The same search continues over the first krcn_lanczos calls of such a
  * handle (unsharded or single-rank, no graph replay, m >= 8): call 1 runs
  * untimed, the next `trials` calls of the same m each run on one placement

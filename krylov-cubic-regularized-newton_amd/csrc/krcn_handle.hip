@@ -343,6 +343,25 @@ extern "C" krcn_status krcn_csr_set_placement_trials(krcn_csr* h, int trials) {
   return KRCN_OK;
 }
 
+extern "C" krcn_status krcn_csr_set_placement_keep(krcn_csr* h, int keep) {
+  // (the range first: it needs no handle, so it can be checked without a device)
+  if (keep < -1 || keep >= krcn_csr::kPlaceMax)
+    return fail(KRCN_ERR_INVALID, "krcn_csr_set_placement_keep: expected -1 (the fastest) or 0..%d (got %d)",
+                krcn_csr::kPlaceMax - 1, keep);
+  if (!h) return fail(KRCN_ERR_INVALID, "krcn_csr_set_placement_keep: null handle");
+  if (h->place_keep != keep) {
+    h->place_keep = keep;
+    h->plans_ready = false;   // applied at the next plan build (and the Lanczos-call search starts over)
+  }
+  return KRCN_OK;
+}
+
+extern "C" krcn_status krcn_csr_get_placement_keep(const krcn_csr* h, int* keep_host) {
+  if (!h || !keep_host) return fail(KRCN_ERR_INVALID, "krcn_csr_get_placement_keep: null argument");
+  *keep_host = h->place_keep;
+  return KRCN_OK;
+}
+
 extern "C" krcn_status krcn_csr_placement_info(krcn_csr* h, double* out24_host) {
   if (!h || !out24_host) return fail(KRCN_ERR_INVALID, "krcn_csr_placement_info: null argument");
   CHK(set_device(h));

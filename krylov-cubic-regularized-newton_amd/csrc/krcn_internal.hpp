@@ -364,6 +364,8 @@ struct krcn_csr {
   // placement probe of the hot buffers (ensure_plans, krcn_csr_set_placement_trials)
   static constexpr int kPlaceMax = 8;
   int place_trials = -1;       // -1 auto, 0 off, k: k placements probed
+  int place_keep = -1;         // -1: the fastest is kept; 0..7: placement min(keep, probed - 1), both searches
+                               //   (krcn_csr_set_placement_keep)
   int place_ran = 0;           // placements probed at the last plan build (0: none)
   int place_best = -1;         // the one kept
   float place_us[kPlaceMax] = {};   // probe HVP time of each (us)

@@ -576,10 +576,11 @@ static krcn_status lanczos_impl(krcn_csr* h, const T* w, const T* g, int m, int 
   CHK(check_lanczos_ws(h, m, reorth));
   const LzStepChoice ch = lanczos_step(lz_step_in(h, reorth));
   CHK(ch.refusal);
-  T* W = static_cast<T*>(h->W);
 
+  // every hot buffer (W, u, the partials) is read in here, after lz_submit's lzp_begin has applied the
+  // placement this call runs and times
   auto enqueue = [&](hipStream_t s) -> krcn_status {
-    LzRun<T> r{h, s, ch, LzCtl<T>{V, g, d, m, 0, 0, h->st, h->betas_dev, h->pb, 0, tol}, w, W,
+    LzRun<T> r{h, s, ch, LzCtl<T>{V, g, d, m, 0, 0, h->st, h->betas_dev, h->pb, 0, tol}, w, static_cast<T*>(h->W),
                static_cast<T*>(h->u), T(h->n_global), T(l2), l2, reorth};
     LzCtl<T>& c = r.c;
     // start (cubic.py:85): zero alphas / betas, partials of ||g||^2 (pass 1 or
@@ -621,10 +622,10 @@ static krcn_status lanczos_impl(krcn_csr* h, const T* w, const T* g, int m, int 
   // krcn_crn_step: the launches alone, eager and outside the placement search;
   // the caller synchronises and reads the results block (lanczos_results)
   if (enqueue_only) return enqueue(s_call);
-  // unsharded, unprofiled calls may replay
+  // unsharded, unprofiled calls may replay (a replaying handle is outside the placement search, so W stays put)
   const bool graph = h->graph && h->shard == KRCN_SHARD_NONE && !h->prof;
   const uint64_t key[krcn_csr::kGraphKey] = {uint64_t(uintptr_t(w)), uint64_t(uintptr_t(g)), uint64_t(uintptr_t(V)),
-                                             uint64_t(uintptr_t(W)), uint64_t(m), uint64_t(reorth), bits(tol),
+                                             uint64_t(uintptr_t(h->W)), uint64_t(m), uint64_t(reorth), bits(tol),
                                              bits(l2), h->ws_gen, uint64_t(sizeof(T))};
   bool lzp_timed = false;
   CHK(lz_submit(h, graph, key, m, s_call, enqueue, &lzp_timed));

@@ -18,6 +18,7 @@ extern "C" krcn_status krcn_matvec(krcn_csr* h, const void* x, void* Ax, void* s
   if (!h || (!x && h->d) || (!Ax && h->n)) return fail(KRCN_ERR_INVALID, "krcn_matvec: null argument");
   CHK(set_device(h));
   if (h->n == 0) return KRCN_OK;
+  CHK(plans_for_compute(h));   // before any scratch pointer is read: a plan build may move them
   return h->dtype == KRCN_F64
              ? matvec_impl<double>(h, static_cast<const double*>(x), static_cast<double*>(Ax), S(stream))
              : matvec_impl<float>(h, static_cast<const float*>(x), static_cast<float*>(Ax), S(stream));
@@ -48,6 +49,7 @@ static krcn_status rmatvec_impl(krcn_csr* h, const T* u, T* y, hipStream_t s) {
 extern "C" krcn_status krcn_rmatvec(krcn_csr* h, const void* u, void* y, void* stream) {
   if (!h || (!u && h->n) || (!y && h->d)) return fail(KRCN_ERR_INVALID, "krcn_rmatvec: null argument");
   CHK(set_device(h));
+  if (h->d) CHK(plans_for_compute(h));   // before any scratch pointer is read: a plan build may move them (td: xt_pass)
   return h->dtype == KRCN_F64
              ? rmatvec_impl<double>(h, static_cast<const double*>(u), static_cast<double*>(y), S(stream))
              : rmatvec_impl<float>(h, static_cast<const float*>(u), static_cast<float*>(y), S(stream));
@@ -94,6 +96,7 @@ extern "C" krcn_status krcn_hvp(krcn_csr* h, const void* w, const void* v, void*
   if (!h || (h->n && !w) || (h->d && (!v || !y))) return fail(KRCN_ERR_INVALID, "krcn_hvp: null argument");
   CHK(set_device(h));
   if (h->d == 0) return KRCN_OK;
+  CHK(plans_for_compute(h));   // before any scratch pointer is read: a plan build may move them (u, td)
   return h->dtype == KRCN_F64
              ? hvp_impl<double>(h, static_cast<const double*>(w), static_cast<const double*>(v),
                                 static_cast<double*>(y), l2, S(stream))
@@ -162,6 +165,9 @@ extern "C" krcn_status krcn_gradient(krcn_csr* h, const void* Ax, const void* b,
   if (!h || (h->n && (!Ax || !b)) || (h->d && !grad) || (l2 != 0.0 && h->d && !x))
     return fail(KRCN_ERR_INVALID, "krcn_gradient: null argument");
   CHK(set_device(h));
+  // before any scratch pointer is read (tn, td) and before the residual is queued into tn: a plan build
+  // may move them, and its placement probe zero-fills tn and W
+  if (h->d) CHK(plans_for_compute(h));
   return h->dtype == KRCN_F64
              ? gradient_impl<double>(h, static_cast<const double*>(Ax), static_cast<const double*>(b),
                                      static_cast<const double*>(x), l2, static_cast<double*>(grad), S(stream))

@@ -86,6 +86,17 @@ static int place_auto_trials(const krcn_csr* h) {
   return std::min(k, krcn_csr::kPlaceMax);
 }
 
+// The placement kept of `ran` timed ones: the fastest, or the one
+// krcn_csr_set_placement_keep names (clamped to those that ran).
+static int kept_placement(const krcn_csr* h, const float* t, int ran) {
+  if (ran <= 0) return 0;
+  if (h->place_keep >= 0) return std::min(h->place_keep, ran - 1);
+  int best = 0;
+  for (int i = 1; i < ran; ++i)
+    if (t[i] < t[best]) best = i;
+  return best;
+}
+
 static void free_placements(std::vector<std::vector<void*>>& cand, int keep) {
   for (size_t t = 0; t < cand.size(); ++t)
     if (int(t) != keep)
@@ -106,6 +117,13 @@ krcn_status tune_placement(krcn_csr* h) {
   hipStream_t s = nullptr;
   HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
   krcn_status r = KRCN_OK;
+  // The probe writes the handle's scratch (it zero-fills tn and W, its HVPs
+  // store u and td) on a stream of its own.  Every entry point builds the
+  // plans before it queues work of its own (plans_for_compute at its top), so
+  // only earlier calls on the caller's streams can still be reading or
+  // writing that scratch when a rebuild starts: wait for them here (a build
+  // need not free anything, so hipFree's implicit wait is not relied on).
+  if (hipDeviceSynchronize() != hipSuccess) r = fail(KRCN_ERR_HIP, "placement probe: device synchronisation");
   // the probe's operands: zero vectors (the traffic does not depend on them)
   for (void** f : {&h->tn, &h->W})
     if (r == KRCN_OK && hipMemsetAsync(*f, 0, h->own.find(f)->bytes, s) != hipSuccess)
@@ -122,9 +140,7 @@ krcn_status tune_placement(krcn_csr* h) {
   }
   if (hipStreamSynchronize(s) != hipSuccess && r == KRCN_OK) r = fail(KRCN_ERR_HIP, "placement probe: sync");
   (void)hipStreamDestroy(s);
-  int best = 0;
-  for (int t = 1; t < h->place_ran; ++t)
-    if (h->place_us[t] < h->place_us[best]) best = t;
+  int best = kept_placement(h, h->place_us, h->place_ran);
   if (r != KRCN_OK) best = 0;   // a failed probe keeps the built placement
   ps.apply(cand[best]);
   free_placements(cand, best);
@@ -211,9 +227,7 @@ krcn_status lzp_done(krcn_csr* h, bool timed) {   // after the call's stream syn
   h->lzp_ran = t + 1;
   ++h->lzp_stage;
   if (h->lzp_ran == place_auto_trials(h)) {
-    int best = 0;
-    for (int i = 1; i < h->lzp_ran; ++i)
-      if (h->lzp_ms[i] < h->lzp_ms[best]) best = i;
+    const int best = kept_placement(h, h->lzp_ms, h->lzp_ran);
     PlaceSet ps;
     ps.init(h);
     ps.apply(h->lzp_cand[size_t(best)]);

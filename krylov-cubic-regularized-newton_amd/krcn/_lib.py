@@ -83,6 +83,8 @@ SIGNATURES = {
     "krcn_csr_plan_value_bytes": [_vp, ctypes.POINTER(ctypes.c_int)],
     "krcn_csr_set_graph": [_vp, _i],
     "krcn_csr_set_placement_trials": [_vp, _i],
+    "krcn_csr_set_placement_keep": [_vp, _i],
+    "krcn_csr_get_placement_keep": [_vp, ctypes.POINTER(ctypes.c_int)],
     "krcn_csr_placement_info": [_vp, _dp],
     "krcn_csr_plan_info": [_vp, ctypes.POINTER(ctypes.c_int)],
     "krcn_csr_plan_format": [_vp, ctypes.POINTER(ctypes.c_int)],

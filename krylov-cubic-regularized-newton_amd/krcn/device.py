@@ -164,16 +164,26 @@ class DeviceCSR:
         call("krcn_csr_set_placement_trials", self._h, int(trials))
         self._replan()
 
+    def set_placement_keep(self, keep=-1):
+        """Which probed placement is kept (krcn_csr_set_placement_keep): -1 the fastest, 0..7 placement
+        min(keep, probed - 1) whatever the timings say, at plan builds and after the Lanczos-call search."""
+        call("krcn_csr_set_placement_keep", self._h, int(keep))
+        self._replan()
+
     def placement_info(self):
-        """The placement probe of the last plan build ({'probed', 'kept', 'hot_mb', 'policy', 'us': [per
-        placement, probe HVP]}) and the search over the first Lanczos calls ({'lanczos': {'timed', 'kept',
-        'm', 'ms': [per placement, one call each]}})."""
+        """The placement probe of the last plan build ({'probed', 'kept', 'hot_mb', 'policy', 'keep', 'us':
+        [per placement, probe HVP]}) and the search over the first Lanczos calls ({'lanczos': {'timed',
+        'kept', 'm', 'stage', 'ms': [per placement, one call each]}}; stage 0: not started, s >= 1: the next
+        eligible call times placement s - 1, -1: finished)."""
         buf = (ctypes.c_double * 24)()
         call("krcn_csr_placement_info", self._h, buf)
+        keep = ctypes.c_int(-1)   # (the 24 doubles are all taken: the override has a getter of its own)
+        call("krcn_csr_get_placement_keep", self._h, ctypes.byref(keep))
         k, kl = int(buf[0]), int(buf[12])
         return {"probed": k, "kept": int(buf[1]), "hot_mb": round(buf[2], 1), "policy": int(buf[3]),
+                "keep": int(keep.value),
                 "us": [round(buf[4 + i], 2) for i in range(k)],
-                "lanczos": {"timed": kl, "kept": int(buf[13]), "m": int(buf[14]),
+                "lanczos": {"timed": kl, "kept": int(buf[13]), "m": int(buf[14]), "stage": int(buf[15]),
                             "ms": [round(buf[16 + i], 4) for i in range(kl)]}}
 
     def plan_info(self):
