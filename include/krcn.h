@@ -508,6 +508,62 @@ krcn_status krcn_lanczos(krcn_csr* h, const void* w, const void* g, int m,
                          double* alphas_host, double* betas_host,
                          krcn_lanczos_info* info_host, void* stream);
 
+/* ---- batched Lanczos: k recurrences in lockstep over the block HVP --------- */
+/* SYNCHRONOUS on return of alphas/betas/info.  k independent recurrences of
+ * krcn_lanczos (reorth = 0) over one X, advanced together: every step runs one
+ * krcn_hvp_block for all columns (m of them per call: m - 1 loop steps and the
+ * final quotient) and at most three vector launches over (d, k) blocks; control
+ * stays on the device and the call synchronises once, at its end.  Not a
+ * block-Krylov method: column c is the reference's Lanczos(A_c, G[:, c], m)
+ * with A_c = v -> X^T (w_c (.) X v) / n + l2_c v, every quirk included, and its
+ * results do not depend on what the other columns hold (bitwise), nor on the
+ * run.  Per column the outcome is what krcn_lanczos(h, w_c, G[:, c], m, 0, tol,
+ * l2_c, ..) defines: the absolute |beta| < tol test, truncation only when
+ * j < m - 2, a zero last vector and betas[m - 2] = 0 for a breakdown at
+ * j == m - 2, the final alphas[m_eff - 1] = v.A(v) on the column's current v,
+ * zeros past m_eff / m_eff - 1, one Rayleigh quotient for m = 1; info_host[c]
+ * as krcn_lanczos fills it (hvps: what the single call would report for the
+ * column, not the block HVPs run).  The sums run in another fixed order than
+ * krcn_lanczos's, so the values agree at the rounding level, not bitwise.
+ * A column that has broken down is frozen: its alphas, betas and state stop
+ * changing and its v is never divided by the tiny beta.
+ * Layouts: G a (d, k) block (element (i, c) at i * k + c); w an n-vector
+ * (w_cols = 1) or an (n, k) block (w_cols = k); l2_host k HOST doubles (NULL:
+ * all zero); V m slabs of (d, k), element (j, i, c) at (j * d + i) * k + c (a
+ * C-contiguous (m, d, k) tensor; slab j is a block-HVP operand);
+ * alphas_host[k * m], row c at c * m; betas_host[k * max(m - 1, 1)], row c at
+ * c * max(m - 1, 1); info_host[k].  The call writes column c of every slab:
+ * its basis vectors, and zeros in every slab that holds none of column c,
+ * whatever V held before, so krcn_basis_combine_block may run over all m slabs
+ * with s zero-padded.  A zero start column gives NaNs in that column.
+ * Both dtypes, scalars in double.  Builds no pass plans and does not touch the
+ * handle's scratch vectors or the results block of krcn_lanczos.  Workspace:
+ * two (d, k) blocks, 393,216 bytes of partials and a results block of
+ * k (2 m + 3 (+ 1 when m = 1)) doubles (with a pinned host mirror), in the
+ * handle's owner table, counted by krcn_csr_owned_bytes, grown only when k or
+ * the results block grows, freed by krcn_csr_destroy; krcn_hvp_block's (n, k)
+ * intermediate as there.  A second call with the same (k, m) allocates nothing.
+ * KRCN_ERR_INVALID before any HIP call: k outside 1..KRCN_BLOCK_MAX, m outside
+ * 1..2044, w_cols neither 1 nor k, a null handle, a null array.  Sharded
+ * handles: KRCN_ERR_UNSUPPORTED.
+ * Replaces k calls of Lanczos, cubic.py:77-111 (cubic_newton.py:67-73 runs
+ * two problems over one matrix). */
+krcn_status krcn_lanczos_block(krcn_csr* h, int k, const void* w, int w_cols, const void* G, int m,
+                               double tol, const double* l2_host, void* V,
+                               double* alphas_host, double* betas_host,
+                               krcn_lanczos_info* info_host, void* stream);
+/* Xnew[i, c] = X0[i, c] + sum_j V[j, i, c] * s[j * k + c], j ascending over all
+ * m slabs (zero-pad s past a column's m_eff): per column krcn_basis_combine's
+ * sum, bit for bit.  s_host: (m, k) HOST doubles, read before the call
+ * returns.  X0 and Xnew are (d, k) blocks.  Replaces x + V @ s_new,
+ * cubic.py:291,301, k times. */
+krcn_status krcn_basis_combine_block(krcn_csr* h, int k, int m, const void* V, const double* s_host,
+                                     const void* X0, void* Xnew, void* stream);
+/* W = s (1 - s), s = expit(AX), over the n k entries of AX = X xs (an (n, k)
+ * block, krcn_matvec_block's result for k iterates): krcn_weights column by
+ * column, bit for bit.  Replaces loss.py:296-297, k times. */
+krcn_status krcn_weights_block(krcn_csr* h, int k, const void* AX, void* W, void* stream);
+
 /* x_new = x + V^T s over the first m_eff basis rows (the reference's
  * x + V @ s_new, cubic.py:291,301).  V is the handle's basis (m rows x local d),
  * s_host an m_eff-vector on the host; x, x_new are local d-vectors. */

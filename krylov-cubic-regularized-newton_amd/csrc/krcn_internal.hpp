@@ -8,6 +8,8 @@
 //   krcn_ops.hip         objective pieces (Ax, X^T u, weights, HVP, gradient, loss, dots)
 //   krcn_coord.hip       coordinate blocks of SSCN (gradient, Hessian block, Ax update)
 //   krcn_block.hip       block products: k vectors per pass over the matrix (X V, X^T U / n, the block HVP)
+//   krcn_lanczos_block.hip  the batched Lanczos: k recurrences in lockstep over the block HVP (krcn_blz.hpp;
+//                        its per-column state rule, krcn_blz_state.hpp, is host-only like the three below)
 //   krcn_crn.hip         the device cubic subproblem and the one-call Krylov-CRN step (krcn_cubic.hpp)
 //   krcn_lanczos_f64.hip / krcn_lanczos_f32.hip
 //                        the device Lanczos recurrence (krcn_lanczos_impl.hpp), one dtype each
@@ -342,6 +344,16 @@ struct krcn_csr {
   int* blk_long[2] = {};      // block products: rows of X / X^T above KRCN_BLOCK_LONG_ROW, listed at the
   int blk_nlong[2] = {};      //   first pass over that matrix (null while there is none)
   bool blk_listed[2] = {};
+  // krcn_lanczos_block (krcn_lanczos_block.hip): grown when k, or k and m, grow
+  void* blz_y = nullptr;      //   (d, blz_k) block: the block HVP's result
+  void* blz_op = nullptr;     //   (d, blz_k) block: the final quotient's operand
+  int blz_k = 0;
+  double* blz_pa = nullptr;   //   per-workgroup partials of the two alpha sums, and of ||z||^2 behind them
+  double* blz_res = nullptr;  //   k states | alphas | betas (blz_res_cap doubles)
+  double* blz_s = nullptr;    //   krcn_basis_combine_block: the (m, k) coefficients (blz_s_cap doubles)
+  size_t blz_res_cap = 0, blz_s_cap = 0;
+  double* blz_host = nullptr; //   pinned, mapped host copy of blz_res that the last launch writes
+  double* blz_host_dev = nullptr;
   DevOwner own;               // every device buffer above but betas_dev (it aliases alphas_dev)
   krcn_comm* comm = nullptr;
   bool prof = false;

@@ -109,6 +109,10 @@ SIGNATURES = {
     "krcn_hvp_block": [_vp, _i, _vp, _i, _vp, _vp, _dp, _vp],
     "krcn_lanczos": [_vp, _vp, _vp, _i, _i, _d, _d, _vp, _dp, _dp,
                      ctypes.POINTER(LanczosInfo), _vp],
+    "krcn_lanczos_block": [_vp, _i, _vp, _i, _vp, _i, _d, _dp, _vp, _dp, _dp,
+                           ctypes.POINTER(LanczosInfo), _vp],
+    "krcn_basis_combine_block": [_vp, _i, _i, _vp, _dp, _vp, _vp, _vp],
+    "krcn_weights_block": [_vp, _i, _vp, _vp, _vp],
     "krcn_basis_combine": [_vp, _i, _vp, _dp, _vp, _vp, _vp],
     "krcn_dot": [_vp, _i, _vp, _vp, _dp, _vp],
     "krcn_diff_norm": [_vp, _i, _vp, _vp, _dp, _vp],

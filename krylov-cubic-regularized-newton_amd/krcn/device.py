@@ -443,6 +443,72 @@ class DeviceCSR:
         me = info.m_eff
         return V, al_b[:me].copy(), be_b[:max(me - 1, 0)].copy(), info
 
+    # -- batched Lanczos: k recurrences in lockstep over the block HVP --------
+    def lanczos_block(self, w, G, m, tol=1e-6, l2=0.0, V=None):
+        """k independent Lanczos recurrences over one X, advanced together
+        (krcn_lanczos_block): column c is `lanczos(w_c, G[:, c], m, l2=l2_c)`.
+
+        w: (n,) weights shared by every column, or an (n, k) block; G: (d, k)
+        start block; l2: a float or a length-k sequence.  Returns (V, alphas,
+        betas, infos): V a device tensor (m, d, k), slab j column c the
+        reference's V[:, j] of problem c and zero where problem c has no basis
+        vector; alphas, betas, infos length-k lists, truncated per column as
+        `lanczos` truncates."""
+        m = int(m)
+        if m < 1:
+            raise ValueError("m must be >= 1")
+        k = int(self._check_block(G, self.d, None, "G").shape[1])
+        if isinstance(w, torch.Tensor) and w.dim() == 2:
+            w_cols = int(self._check_block(w, self.n, None, "w").shape[1])
+        else:
+            self._check(w, self.n, "w")
+            w_cols = 1
+        if np.ndim(l2) == 0:
+            l2s = np.full(max(k, 1), float(l2), dtype=np.float64)
+        else:
+            l2s = np.ascontiguousarray(np.asarray(l2, dtype=np.float64).reshape(-1))
+            if len(l2s) != k:
+                raise ValueError(f"l2 must be a float or have one entry per column ({k}), got {len(l2s)}")
+        if V is None:
+            V = torch.empty((m, self.d, k), dtype=self.dtype, device=self.device)
+        elif (not isinstance(V, torch.Tensor) or V.dtype != self.dtype or V.device != self.device
+              or not V.is_contiguous() or tuple(V.shape) != (m, self.d, k)):
+            raise ValueError(f"V must be a contiguous ({m}, {self.d}, {k}) {self.dtype} tensor on {self.device}")
+        mb = max(m - 1, 1)
+        al = np.zeros((max(k, 1), m), dtype=np.float64)
+        be = np.zeros((max(k, 1), mb), dtype=np.float64)
+        infos = (_lib.LanczosInfo * max(k, 1))()
+        call("krcn_lanczos_block", self._h, k, _ptr(w), w_cols, _ptr(G), m, float(tol), l2s.ctypes.data_as(_lib._dp),
+             _ptr(V), al.ctypes.data_as(_lib._dp), be.ctypes.data_as(_lib._dp), infos, _stream(self.device))
+        alphas = [al[c, :infos[c].m_eff].copy() for c in range(k)]
+        betas = [be[c, :max(infos[c].m_eff - 1, 0)].copy() for c in range(k)]
+        return V, alphas, betas, [infos[c] for c in range(k)]
+
+    def basis_combine_block(self, V, S, X0, out=None):
+        """X0[:, c] + sum_j V[j, :, c] S[j, c] over the slabs of a lanczos_block
+        basis (krcn_basis_combine_block).  S: (m', k) host coefficients, m' <=
+        V.shape[0], zero-padded past a column's m_eff."""
+        S = np.ascontiguousarray(S, dtype=np.float64)
+        if S.ndim != 2:
+            raise ValueError("S must be (m, k)")
+        mm, k = int(S.shape[0]), int(S.shape[1])
+        self._check_block(X0, self.d, k, "X0")
+        if (not isinstance(V, torch.Tensor) or V.dtype != self.dtype or V.device != self.device or V.dim() != 3
+                or not V.is_contiguous() or V.shape[0] < mm or tuple(V.shape[1:]) != (self.d, k)):
+            raise ValueError(f"V must be a contiguous (>= {mm}, {self.d}, {k}) {self.dtype} tensor on {self.device}")
+        out = self._block_out(out, self.d, k)
+        call("krcn_basis_combine_block", self._h, k, mm, _ptr(V), S.ctypes.data_as(_lib._dp), _ptr(X0), _ptr(out),
+             _stream(self.device))
+        return out
+
+    def weights_block(self, AX, out=None):
+        """W = s (1 - s), s = expit(AX), for an (n, k) block AX = X xs
+        (krcn_weights_block): `weights` column by column."""
+        k = int(self._check_block(AX, self.n, None, "AX").shape[1])
+        out = self._block_out(out, self.n, k)
+        call("krcn_weights_block", self._h, k, _ptr(AX), _ptr(out), _stream(self.device))
+        return out
+
     def cg_solve(self, w, b, shift=0.0, rtol=1e-5, maxiter=None, out=None):
         """x ~= (H + shift I)^{-1} b, H = X^T diag(w) X / n, by device conjugate
         gradients with scipy.sparse.linalg.cg's loop and stopping rule (x0 = 0,

@@ -401,6 +401,36 @@ class LogisticRegression(Oracle):
             out[:, c0:c1] = X.hvp_block(w, Vd[:, c0:c1].contiguous(), l2=float(self.l2))
         return out if is_torch else self.to_host(out)
 
+    def lanczos_block(self, xs, G, m, l2=None):
+        """k Lanczos recurrences (cubic.py:77-111) over this matrix in lockstep
+        (krcn_lanczos_block), column c started from G[:, c].  xs of shape (d,):
+        one iterate, its weights shared by every column; xs of shape (d, k): k
+        iterates, column c on the Hessian at xs[:, c] (one block product X xs,
+        then the block weights).  l2: a float or one per column (default: this
+        loss's l2 for every column).  Returns (V, alphas, betas, infos) as
+        DeviceCSR.lanczos_block; numpy G -> numpy V of shape (m, d, k)."""
+        self._no_shards("lanczos_block")
+        is_torch = isinstance(G, torch.Tensor)
+        if G.ndim != 2 or G.shape[0] != self.dim or not 1 <= G.shape[1] <= _lib.KRCN_BLOCK_MAX:
+            raise ValueError(f"G must be a ({self.dim}, k) block with 1 <= k <= {_lib.KRCN_BLOCK_MAX}, "
+                             f"got shape {tuple(G.shape)}")
+        k = int(G.shape[1])
+        X = self.device_matrix
+
+        def block(a):
+            if isinstance(a, torch.Tensor):
+                return a.to(device=self.device, dtype=self.dtype).contiguous()
+            return torch.from_numpy(np.ascontiguousarray(a, dtype=self._np_dtype())).to(self.device)
+
+        if xs.ndim == 1:
+            w = self._weights_for(xs)
+        elif xs.ndim == 2 and tuple(xs.shape) == (self.dim, k):
+            w = X.weights_block(X.matvec_block(block(xs)))
+        else:
+            raise ValueError(f"xs must have shape ({self.dim},) or ({self.dim}, {k}), got {tuple(xs.shape)}")
+        V, alphas, betas, infos = X.lanczos_block(w, block(G), m, l2=float(self.l2) if l2 is None else l2)
+        return (V if is_torch else self.to_host(V)), alphas, betas, infos
+
     def hess_operator(self, x):
         return HessianOperator(self, x)
 
