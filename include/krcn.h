@@ -627,6 +627,79 @@ krcn_status krcn_crn_step(krcn_csr* h, const void* x, const void* b, const void*
                           void* x_new, void* Ax_new, double* alphas_host, double* betas_host,
                           krcn_crn_info* info_host, void* stream);
 
+/* ---- the batched Krylov-CRN step: k problems over one X per call ---------- */
+/* The batch forms of krcn_gradient, the loss value, krcn_cubic_tridiag and
+ * krcn_crn_step over the (L, k) blocks of the block products (element (i, c)
+ * at i * k + c, 1 <= k <= KRCN_BLOCK_MAX), both dtypes, scalars in double.
+ * Unsharded handles only (KRCN_ERR_UNSUPPORTED otherwise).  Argument errors are
+ * KRCN_ERR_INVALID before any HIP call, and the scalar ranges (k, m, b_cols,
+ * max_trials, ls_beta, solver_it_max, it_max) are checked before the handle is
+ * looked at.  Per-column reductions are two-stage in krcn_lanczos_block's fixed
+ * order (no atomics): a column's bytes depend on k's lane group (the next
+ * power of two >= k) and not on what the other columns hold.  The calls build
+ * no pass plans.  Workspace: a (d, k) and an (n, k) block and 3 k 2044 doubles
+ * of subproblem vectors, grown only when k grows, and fixed blocks for the
+ * state, the partials (262,144 bytes) and a pinned host record block; all in the
+ * handle's owner table, counted by krcn_csr_owned_bytes, freed by
+ * krcn_csr_destroy, apart from u / tn / W / td, krcn_crn_step's workspace and
+ * krcn_lanczos's results block.  A second call with the same (k, m) allocates
+ * nothing. */
+/* G[:, c] = X^T (expit(AX[:, c]) - b_c) / n + l2_c X[:, c].  b_cols = 1: one
+ * label n-vector for every column; b_cols = k: an (n, k) block of 0/1 labels
+ * (one-vs-rest).  l2_host: k HOST doubles (NULL: all zero); a column with
+ * l2_c == 0 never reads X, which may be NULL when every l2_c is zero.
+ * Replaces k calls of gradient, loss.py:223-232. */
+krcn_status krcn_gradient_block(krcn_csr* h, int k, const void* AX, const void* b, int b_cols,
+                                const void* X, const double* l2_host, void* G, void* stream);
+/* SYNCHRONOUS.  values_host[c] = mean_i((1 - b_c) a - logsig(a)) + l2_c / 2 ||X[:, c]||^2
+ * over a = AX[:, c].  Replaces k calls of value, loss.py:215-220. */
+krcn_status krcn_value_block(krcn_csr* h, int k, const void* AX, const void* b, int b_cols, const void* X,
+                             const double* l2_host, double* values_host, void* stream);
+/* SYNCHRONOUS.  k subproblems of krcn_cubic_tridiag in one launch, one
+ * workgroup per column: column c solves over its first m_eff_host[c] <= m
+ * entries (row c of alphas_host / s_host at c * m, of betas_host at
+ * c * max(m - 1, 1)) with gnorm_host[c], M_host[c] and r0_host[c]; per column
+ * s (zero past m_eff_c, zero when the solve failed) and the solver fields of
+ * info_host[c] are bitwise what krcn_cubic_tridiag returns for that column's
+ * inputs.  Replaces k calls of cubic_solver_root, cubic.py:40-75. */
+krcn_status krcn_cubic_tridiag_block(krcn_csr* h, int k, int m, const int* m_eff_host,
+                                     const double* alphas_host, const double* betas_host,
+                                     const double* gnorm_host, const double* M_host, const double* r0_host,
+                                     double eps, int it_max, double* s_host, krcn_crn_info* info_host,
+                                     void* stream);
+/* SYNCHRONOUS.  One Krylov-CRN step of k problems over one X.  Column c is what
+ * krcn_crn_step(h, X[:, c], b_c, AX[:, c], values_host[c], m, 0, tol, l2_c,
+ * reg_coef_host[c], ls_beta, r0_host[c], ..) defines: the same line search
+ * (M = reg_coef_c * ls_beta, divided by ls_beta per rejected trial, at most
+ * max_trials of them), the same truncation of the subproblem to the column's
+ * m_eff and the same krcn_crn_info fields, with `lanczos` as krcn_lanczos_block
+ * fills it.  The recurrence is krcn_lanczos_block's, so values agree with the
+ * single call at the rounding level, not bitwise.  X (d, k), AX (n, k) or NULL
+ * (then X X is formed), V (m, d, k) as krcn_lanczos_block, X_new (d, k) and
+ * AX_new (n, k) that alias no input; values_host, reg_coef_host, r0_host: k HOST
+ * doubles; l2_host: k doubles or NULL; alphas_host[k * m] and
+ * betas_host[k * max(m - 1, 1)] as krcn_lanczos_block returns them, or NULL.
+ * active_host (k ints, NULL: all active): a column with active_host[c] == 0
+ * starts as done: X_new[:, c] / AX_new[:, c] are byte copies of the inputs
+ * (of X X[:, c] when AX is NULL), its info reports accepted = 0, trials = 0,
+ * value_new = values_host[c], reg_coef = reg_coef_host[c], dx_norm = 0, and
+ * whatever the recurrence computes in that column reaches no other column.
+ * A column whose solve fails (solver_status 1 or 2) ends its own chain only;
+ * its X_new / AX_new column is unspecified and its dx_norm 0.  The decisions
+ * are taken per column on the device; a column that has ended keeps the
+ * iterate it accepted (the last trial's at the cap) while the others go on.
+ * The host enqueues trials 0 and 1, then batches of four, and synchronises
+ * once per batch.  No reorthogonalisation; no graph replay or placement search
+ * inside the call.
+ * Replaces k calls of Cubic_Krylov_LS.step, cubic.py:265-309
+ * (cubic_newton.py:67-73 runs two problems over one matrix). */
+krcn_status krcn_crn_step_block(krcn_csr* h, int k, const void* X, const void* b, int b_cols, const void* AX,
+                                const double* values_host, const int* active_host, int m, double tol,
+                                const double* l2_host, const double* reg_coef_host, double ls_beta,
+                                const double* r0_host, double solver_eps, int solver_it_max, int max_trials,
+                                void* V, void* X_new, void* AX_new, double* alphas_host, double* betas_host,
+                                krcn_crn_info* info_host, void* stream);
+
 /* ---- dense vector helpers (host glue of optimizer.py / utils.py) -------- */
 /* Vector spaces of a handle: n-vectors (one entry per sample row) and
  * d-vectors (one entry per feature).  In a sharded handle the helper reduces

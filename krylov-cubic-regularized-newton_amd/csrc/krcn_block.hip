@@ -136,6 +136,32 @@ extern "C" krcn_status krcn_rmatvec_block(krcn_csr* h, int k, const void* U, voi
              : rmatvec_block_impl<float>(h, k, static_cast<const float*>(U), static_cast<float*>(Y), S(stream));
 }
 
+// ------------------------------- the batched Krylov-CRN step's passes
+krcn_status block_rmatvec_l2(krcn_csr* h, int k, const void* U, const void* Xv, const double* l2_host, void* Y,
+                             hipStream_t s) {
+  auto run = [&](auto zero) -> krcn_status {
+    using T = decltype(zero);
+    const BlkHvpOut<T> out = hvp_out<T>(h, k, static_cast<const T*>(Xv), static_cast<T*>(Y), l2_host);
+    if (block_empty(h)) {
+      hipLaunchKernelGGL((k_block_l2v<T>), dim3(vec_grid(h->d * k)), dim3(kNT), 0, s, h->d, k, out);
+      LAUNCHCHK();
+      return KRCN_OK;
+    }
+    return block_pass<T>(h, 1, static_cast<const T*>(U), k, out, s);
+  };
+  return h->dtype == KRCN_F64 ? run(double(0)) : run(float(0));
+}
+
+krcn_status block_matvec_live(krcn_csr* h, int k, const void* V, void* Tn, const double* state, hipStream_t s) {
+  const CrnbHead* head = reinterpret_cast<const CrnbHead*>(state);
+  const CrnbCol* cols = reinterpret_cast<const CrnbCol*>(state + sizeof(CrnbHead) / sizeof(double));
+  return h->dtype == KRCN_F64
+             ? block_pass<double>(h, 0, static_cast<const double*>(V), k,
+                                  BlkStoreLive<double>{static_cast<double*>(Tn), head, cols}, s)
+             : block_pass<float>(h, 0, static_cast<const float*>(V), k,
+                                 BlkStoreLive<float>{static_cast<float*>(Tn), head, cols}, s);
+}
+
 // ------------------------------------------------------------- block HVP
 template <typename T>
 static krcn_status hvp_block_impl(krcn_csr* h, int k, const T* w, int w_cols, const T* V, T* Y,

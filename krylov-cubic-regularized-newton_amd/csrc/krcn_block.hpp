@@ -35,11 +35,12 @@
 // Epilogues are functors called once per (row, vector) by the owning lane.
 #pragma once
 #include "krcn_block_rows.hpp"
+#include "krcn_crnb_state.hpp"
 #include "krcn_kernels.hpp"
 
 namespace krcn {
 
-// T[r, j] = s                                  (X V, one krcn_matvec per column)
+// T[r, j] = s                                (X V, one krcn_matvec per column)
 template <typename T> struct BlkStore {
   T* out;
   __device__ __forceinline__ void row(int64_t r, int j, int k, T s) const { out[r * k + j] = s; }
@@ -67,6 +68,24 @@ template <typename T> struct BlkHvpOut {
     y[r * k + j] = l != T(0) ? q + l * v[r * k + j] : q;
   }
 };
+
+// T[r, j] = s for the live columns of a batched Krylov-CRN trial (krcn_crn_block.hip):
+// the launch returns at once when the chain has ended and a column that is no
+// longer live keeps its bytes.  An epilogue with a member type Guarded makes
+// k_block_pass / k_block_long ask stop() first; the other epilogues' kernels
+// are compiled without the question.
+template <typename T> struct BlkStoreLive {
+  using Guarded = void;
+  T* out;
+  const CrnbHead* head;
+  const CrnbCol* cols;
+  __device__ __forceinline__ bool stop() const { return head->all_done != 0; }
+  __device__ __forceinline__ void row(int64_t r, int j, int k, T s) const {
+    if (crnb_live(cols[j].phase)) out[r * k + j] = s;
+  }
+};
+template <class E, class = void> struct BlkGuarded : std::false_type {};
+template <class E> struct BlkGuarded<E, std::void_t<typename E::Guarded>> : std::true_type {};
 
 // Left-to-right sum over elements [b, e) of a_e * V[col_e, j] by one lane group
 // (m: the lane's position in its group, j == m; gathers only when j < k).
@@ -125,6 +144,8 @@ template <typename T, int K, class Epi>
 __global__ __launch_bounds__(kBlockNT) void k_block_pass(int rows, const int* __restrict__ ptr,
                                                          const int* __restrict__ idx, const T* __restrict__ val,
                                                          const T* __restrict__ V, int k, Epi epi) {
+  if constexpr (BlkGuarded<Epi>::value)
+    if (epi.stop()) return;
   constexpr int G = kBlockNT / K;
   const int g = int(threadIdx.x) / K, m = int(threadIdx.x) % K;
   const int64_t r = int64_t(blockIdx.x) * G + g;
@@ -141,6 +162,8 @@ __global__ __launch_bounds__(kBlockLongNT) void k_block_long(const int* __restri
                                                              const int* __restrict__ ptr,
                                                              const int* __restrict__ idx, const T* __restrict__ val,
                                                              const T* __restrict__ V, int k, Epi epi) {
+  if constexpr (BlkGuarded<Epi>::value)
+    if (epi.stop()) return;
   constexpr int G = kBlockLongNT / K;
   __shared__ T part[kBlockLongNT];
   const int g = int(threadIdx.x) / K, m = int(threadIdx.x) % K;

@@ -176,17 +176,22 @@ __device__ __forceinline__ void cubic_backward(int m, const double* e, double* b
 // y = (T + lam I)^{-1} g = -s(lam): negation is exact and the solves are odd,
 // so phi, dphi and s have the host expressions' values.
 // Every loop is bounded by it_max or m; no other workgroup is waited on.
-[[maybe_unused]] static __global__ __launch_bounds__(kNT) void k_cubic_tridiag(CrnState* st,
-                                                                              const double* __restrict__ al_g,
-                                                                              const double* __restrict__ be_g,
-                                                                              double* __restrict__ s_g, double r0,
-                                                                              double eps, int it_max, CrnState* res) {
-  if (st->done) return;
+// The body is a device function of one workgroup (every thread calls it with
+// the same arguments and gets the same result): k_cubic_tridiag runs it on the
+// single chain's state, k_crnb_solve (krcn_crnb.hpp) on one column per
+// workgroup.  s_g receives the m entries of s when the solve succeeded.
+struct CubicSolve {
+  int its, status;
+  double root, dec;
+};
+__device__ __forceinline__ CubicSolve cubic_tridiag_solve(int m, double M, double gnorm,
+                                                          const double* __restrict__ al_g,
+                                                          const double* __restrict__ be_g,
+                                                          double* __restrict__ s_g, double r0, double eps,
+                                                          int it_max) {
   __shared__ double al[kCubicMaxM], be[kCubicMaxM], dd[kCubicMaxM], ee[kCubicMaxM], y[kCubicMaxM], z[kCubicMaxM];
   __shared__ double sm[kNT / 64];
   __shared__ int ok_sm;
-  const int m = st->m_eff;
-  const double M = st->M, gnorm = st->gnorm;
   const int tid = threadIdx.x;
   for (int i = tid; i < m; i += kNT) al[i] = al_g[i];
   for (int i = tid; i + 1 < m; i += kNT) be[i] = be_g[i];
@@ -279,12 +284,22 @@ __device__ __forceinline__ void cubic_backward(int m, const double* e, double* b
       for (int i = tid; i < m; i += kNT) s_g[i] = 0.0 - y[i];
     }
   }
-  if (tid == 0) {
-    st->solver_it = its;
-    st->solver_status = status;
-    st->lam = root;
-    st->model_decrease = dec;
-    if (status == kCubicNotPd || status == kCubicDerZero) st->done = 1;   // nothing to try: the chain ends here
+  return CubicSolve{its, status, root, dec};
+}
+
+[[maybe_unused]] static __global__ __launch_bounds__(kNT) void k_cubic_tridiag(CrnState* st,
+                                                                              const double* __restrict__ al_g,
+                                                                              const double* __restrict__ be_g,
+                                                                              double* __restrict__ s_g, double r0,
+                                                                              double eps, int it_max, CrnState* res) {
+  if (st->done) return;
+  const CubicSolve r = cubic_tridiag_solve(st->m_eff, st->M, st->gnorm, al_g, be_g, s_g, r0, eps, it_max);
+  if (threadIdx.x == 0) {
+    st->solver_it = r.its;
+    st->solver_status = r.status;
+    st->lam = r.root;
+    st->model_decrease = r.dec;
+    if (r.status == kCubicNotPd || r.status == kCubicDerZero) st->done = 1;   // nothing to try: the chain ends here
     *res = *st;
   }
 }

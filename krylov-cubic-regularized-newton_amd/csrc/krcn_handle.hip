@@ -81,6 +81,7 @@ static krcn_status destroy_impl(krcn_csr* h) {
   if (h->hostres) (void)hipHostFree(h->hostres);
   if (h->crn_res) (void)hipHostFree(h->crn_res);
   if (h->blz_host) (void)hipHostFree(h->blz_host);
+  if (h->crnb_host) (void)hipHostFree(h->crnb_host);
   if (h->gexec) (void)hipGraphExecDestroy(h->gexec);
   if (h->gstream) (void)hipStreamDestroy(h->gstream);
   if (h->lzp_e0) (void)hipEventDestroy(h->lzp_e0);

@@ -354,7 +354,16 @@ struct krcn_csr {
   size_t blz_res_cap = 0, blz_s_cap = 0;
   double* blz_host = nullptr; //   pinned, mapped host copy of blz_res that the last launch writes
   double* blz_host_dev = nullptr;
-  DevOwner own;               // every device buffer above but betas_dev (it aliases alphas_dev)
+  // krcn_crn_step_block and its pieces (krcn_crn_block.hip): the blocks grow when k grows
+  void* crnb_g = nullptr;     //   (d, crnb_k) block: the gradients
+  void* crnb_w = nullptr;     //   (n, crnb_k) block: the residuals, then the Hessian weights
+  double* crnb_sub = nullptr; //   the subproblem's alphas | betas | s: 3 crnb_k kLzMaxM doubles
+  int crnb_k = 0;
+  double* crnb_st = nullptr;  //   head | KRCN_BLOCK_MAX records | the staged per-column parameters
+  double* crnb_pa = nullptr;  //   per-workgroup partials of the loss terms, and of the squared norms behind them
+  double* crnb_host = nullptr;   // pinned, mapped host block the judge writes: head | records | k values
+  double* crnb_host_dev = nullptr;
+  DevOwner own;              // every device buffer above but betas_dev (it aliases alphas_dev)
   krcn_comm* comm = nullptr;
   bool prof = false;
   std::vector<ProfRec> prof_pool;
@@ -517,5 +526,24 @@ inline void lanczos_results(const krcn_csr* h, int m, double* alphas_host, doubl
 // The workspace of krcn_cubic_tridiag / krcn_crn_step (krcn_crn.hip): allocated
 // by krcn_csr_reserve and by the first of those calls.
 krcn_status ensure_crn_ws(krcn_csr* h);
+
+// The batched Lanczos in two parts (krcn_lanczos_block.hip): the launches of a
+// call alone — arguments as krcn_lanczos_block's, already checked; no
+// synchronisation after the recurrence —, and the reading of the mapped results
+// block once the stream has passed k_blz_finish (alphas_host / betas_host may
+// be null).  krcn_lanczos_block is the first, a synchronisation and the second.
+krcn_status lanczos_block_enqueue(krcn_csr* h, int k, const void* w, int w_cols, const void* G, int m, double tol,
+                                  const double* l2_host, void* V, hipStream_t s);
+void lanczos_block_results(const krcn_csr* h, int k, int m, double* alphas_host, double* betas_host,
+                           krcn_lanczos_info* info);
+
+// Block passes behind the batched Krylov-CRN step (krcn_block.hip; arguments
+// already checked, no pass plans).  Y = X^T U / n + l2_c Xv[:, c]: the block
+// gradient's product, krcn_rmatvec_block's walk with EpiGrad's expression
+// (BlkHvpOut's, with the iterate as v).  T = X V for the live columns of a
+// trial: a guarded launch that returns at once when the chain has ended.
+krcn_status block_rmatvec_l2(krcn_csr* h, int k, const void* U, const void* Xv, const double* l2_host, void* Y,
+                             hipStream_t s);
+krcn_status block_matvec_live(krcn_csr* h, int k, const void* V, void* Tn, const double* state, hipStream_t s);
 
 #include "krcn_pass.hpp"

@@ -67,12 +67,11 @@ static void blz_lanes(int k, F&& f) {
   }
 }
 
+// The launches of one call (the sequence above), without the synchronisation.
 template <typename T>
-static krcn_status lanczos_block_impl(krcn_csr* h, int k, const T* w, int w_cols, const T* Gm, int m, double tol,
-                                      const double* l2_host, T* V, double* alphas_host, double* betas_host,
-                                      krcn_lanczos_info* info, hipStream_t s) {
+static krcn_status blz_enqueue(krcn_csr* h, int k, const T* w, int w_cols, const T* Gm, int m, double tol,
+                               const double* l2_host, T* V, hipStream_t s) {
   const int64_t d = h->d;
-  const int mb = m > 1 ? m - 1 : 1;
   CHK(blz_reserve(h, k, m, s));
   T* Y = static_cast<T*>(h->blz_y);
   T* op = static_cast<T*>(h->blz_op);
@@ -126,8 +125,21 @@ static krcn_status lanczos_block_impl(krcn_csr* h, int k, const T* w, int w_cols
                        h->blz_host_dev);
   });
   LAUNCHCHK();
-  HIPCHK(hipStreamSynchronize(s));   // the call's one synchronisation
+  return KRCN_OK;
+}
 
+krcn_status lanczos_block_enqueue(krcn_csr* h, int k, const void* w, int w_cols, const void* G, int m, double tol,
+                                  const double* l2_host, void* V, hipStream_t s) {
+  return h->dtype == KRCN_F64
+             ? blz_enqueue<double>(h, k, static_cast<const double*>(w), w_cols, static_cast<const double*>(G), m, tol,
+                                   l2_host, static_cast<double*>(V), s)
+             : blz_enqueue<float>(h, k, static_cast<const float*>(w), w_cols, static_cast<const float*>(G), m, tol,
+                                  l2_host, static_cast<float*>(V), s);
+}
+
+void lanczos_block_results(const krcn_csr* h, int k, int m, double* alphas_host, double* betas_host,
+                           krcn_lanczos_info* info) {
+  const int mb = m > 1 ? m - 1 : 1;
   const double* hb = h->blz_host;
   for (int c = 0; c < k; ++c) {
     BlzCol col;
@@ -136,8 +148,10 @@ static krcn_status lanczos_block_impl(krcn_csr* h, int k, const T* w, int w_cols
     const int m_eff = blz_m_eff(jb, m);
     const double* al = hb + 4 * k + size_t(c) * m;
     const double* be = hb + 4 * k + size_t(k) * m + size_t(c) * mb;
-    for (int i = 0; i < m; ++i) alphas_host[size_t(c) * m + i] = i < m_eff ? al[i] : 0.0;
-    for (int i = 0; i < mb; ++i) betas_host[size_t(c) * mb + i] = (i + 1 < m && i < m_eff - 1) ? be[i] : 0.0;
+    if (alphas_host)
+      for (int i = 0; i < m; ++i) alphas_host[size_t(c) * m + i] = i < m_eff ? al[i] : 0.0;
+    if (betas_host)
+      for (int i = 0; i < mb; ++i) betas_host[size_t(c) * mb + i] = (i + 1 < m && i < m_eff - 1) ? be[i] : 0.0;
     info[c].m_eff = m_eff;
     info[c].breakdown = jb >= 0;
     info[c].j_break = jb >= 0 ? jb : -1;
@@ -145,7 +159,6 @@ static krcn_status lanczos_block_impl(krcn_csr* h, int k, const T* w, int w_cols
     info[c].beta_last = col.beta_last;
     info[c].gnorm = col.gnorm;
   }
-  return KRCN_OK;
 }
 
 extern "C" krcn_status krcn_lanczos_block(krcn_csr* h, int k, const void* w, int w_cols, const void* G, int m,
@@ -162,13 +175,10 @@ extern "C" krcn_status krcn_lanczos_block(krcn_csr* h, int k, const void* w, int
   if (h->shard != KRCN_SHARD_NONE)
     return fail(KRCN_ERR_UNSUPPORTED, "krcn_lanczos_block: implemented for unsharded handles");
   CHK(set_device(h));
-  return h->dtype == KRCN_F64
-             ? lanczos_block_impl<double>(h, k, static_cast<const double*>(w), w_cols, static_cast<const double*>(G), m,
-                                          tol, l2_host, static_cast<double*>(V), alphas_host, betas_host, info_host,
-                                          S(stream))
-             : lanczos_block_impl<float>(h, k, static_cast<const float*>(w), w_cols, static_cast<const float*>(G), m,
-                                         tol, l2_host, static_cast<float*>(V), alphas_host, betas_host, info_host,
-                                         S(stream));
+  CHK(lanczos_block_enqueue(h, k, w, w_cols, G, m, tol, l2_host, V, S(stream)));
+  HIPCHK(hipStreamSynchronize(S(stream)));   // the call's one synchronisation
+  lanczos_block_results(h, k, m, alphas_host, betas_host, info_host);
+  return KRCN_OK;
 }
 
 extern "C" krcn_status krcn_basis_combine_block(krcn_csr* h, int k, int m, const void* V, const double* s_host,

@@ -67,6 +67,7 @@ _i = ctypes.c_int
 _i64 = ctypes.c_int64
 _d = ctypes.c_double
 _dp = ctypes.POINTER(ctypes.c_double)
+_ip = ctypes.POINTER(ctypes.c_int)
 
 # name -> argtypes (every symbol include/krcn.h declares)
 SIGNATURES = {
@@ -125,6 +126,11 @@ SIGNATURES = {
     "krcn_cubic_tridiag": [_vp, _i, _dp, _dp, _d, _d, _d, _d, _i, _dp, ctypes.POINTER(CrnInfo), _vp],
     "krcn_crn_step": [_vp, _vp, _vp, _vp, _d, _i, _i, _d, _d, _d, _d, _d, _d, _i, _i, _vp, _vp, _vp, _dp, _dp,
                       ctypes.POINTER(CrnInfo), _vp],
+    "krcn_gradient_block": [_vp, _i, _vp, _vp, _i, _vp, _dp, _vp, _vp],
+    "krcn_value_block": [_vp, _i, _vp, _vp, _i, _vp, _dp, _dp, _vp],
+    "krcn_cubic_tridiag_block": [_vp, _i, _i, _ip, _dp, _dp, _dp, _dp, _dp, _d, _i, _dp, ctypes.POINTER(CrnInfo), _vp],
+    "krcn_crn_step_block": [_vp, _i, _vp, _vp, _i, _vp, _dp, _ip, _i, _d, _dp, _dp, _d, _dp, _d, _i, _i, _vp, _vp,
+                            _vp, _dp, _dp, ctypes.POINTER(CrnInfo), _vp],
     "krcn_vctx_create": [_i, ctypes.POINTER(_vp)],
     "krcn_vctx_destroy": [_vp],
     "krcn_lz_ext_step": [_vp, _i, _i64, _vp, _vp, _vp, _d, _vp, _dp, _vp],

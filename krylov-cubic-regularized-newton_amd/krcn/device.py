@@ -590,6 +590,134 @@ class DeviceCSR:
         me = info.lanczos.m_eff
         return x_new, Ax_new, al[:me], be[:max(me - 1, 0)], info
 
+    # -- the batched Krylov-CRN step: k problems over one X --------------------
+    @staticmethod
+    def _per_column(v, k, name):
+        """A float or a length-k sequence as k contiguous float64."""
+        if np.ndim(v) == 0:
+            return np.full(max(k, 1), float(v), dtype=np.float64)
+        a = np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1))
+        if len(a) != k:
+            raise ValueError(f"{name} must be a float or have one entry per column ({k}), got {len(a)}")
+        return a
+
+    def _labels(self, b, k):
+        """b as krcn_*_block takes it: an n-vector (b_cols = 1) or an (n, k) block (b_cols = k)."""
+        if isinstance(b, torch.Tensor) and b.dim() == 2:
+            self._check_block(b, self.n, k, "b")
+            return k
+        self._check(b, self.n, "b")
+        return 1
+
+    def gradient_block(self, AX, b, X=None, l2=0.0, out=None):
+        """G[:, c] = X^T (expit(AX[:, c]) - b_c) / n + l2_c X[:, c] for an (n, k)
+        block AX (krcn_gradient_block): `gradient` column by column.  b: (n,)
+        labels shared by every column, or an (n, k) block of 0/1 labels; l2: a
+        float or a length-k sequence; X: the (d, k) iterates, needed where some
+        l2_c != 0."""
+        k = int(self._check_block(AX, self.n, None, "AX").shape[1])
+        b_cols = self._labels(b, k)
+        l2s = self._per_column(l2, k, "l2")
+        if l2s.any():
+            self._check_block(X, self.d, k, "X")
+        out = self._block_out(out, self.d, k)
+        call("krcn_gradient_block", self._h, k, _ptr(AX), _ptr(b), b_cols, _ptr(X), l2s.ctypes.data_as(_lib._dp),
+             _ptr(out), _stream(self.device))
+        return out
+
+    def value_block(self, AX, b, X=None, l2=0.0):
+        """f_c = mean((1 - b_c) a - logsig(a)) + l2_c / 2 ||X[:, c]||^2 over a =
+        AX[:, c] (krcn_value_block): a numpy (k,) array, one loss value per column."""
+        k = int(self._check_block(AX, self.n, None, "AX").shape[1])
+        b_cols = self._labels(b, k)
+        l2s = self._per_column(l2, k, "l2")
+        if l2s.any():
+            self._check_block(X, self.d, k, "X")
+        out = np.zeros(max(k, 1), dtype=np.float64)
+        call("krcn_value_block", self._h, k, _ptr(AX), _ptr(b), b_cols, _ptr(X), l2s.ctypes.data_as(_lib._dp),
+             out.ctypes.data_as(_lib._dp), _stream(self.device))
+        return out[:k]
+
+    def cubic_tridiag_block(self, alphas, betas, gnorm, M, r0=0.1, eps=1e-8, it_max=100):
+        """k subproblems of `cubic_tridiag` in one launch (krcn_cubic_tridiag_block).
+        alphas / betas: length-k lists of arrays (column c has len(alphas[c]) =
+        m_eff_c entries and m_eff_c - 1 betas); gnorm, M, r0: floats or length-k
+        sequences.  Returns (s, infos): s a list of numpy (m_eff_c,) arrays,
+        infos a list of _lib.CrnInfo; per column bitwise `cubic_tridiag`."""
+        k = len(alphas)
+        if len(betas) != k:
+            raise ValueError("alphas and betas must list the same number of columns")
+        als = [np.asarray(a, dtype=np.float64).reshape(-1) for a in alphas]
+        bes = [np.asarray(a, dtype=np.float64).reshape(-1) for a in betas]
+        m = max([len(a) for a in als] + [1])
+        mb = max(m - 1, 1)
+        al = np.zeros((max(k, 1), m), dtype=np.float64)
+        be = np.zeros((max(k, 1), mb), dtype=np.float64)
+        m_eff = np.ones(max(k, 1), dtype=np.int32)
+        for c in range(k):
+            if len(als[c]) < 1 or len(bes[c]) != len(als[c]) - 1:
+                raise ValueError(f"column {c}: betas must have len(alphas) - 1 entries and alphas at least one")
+            m_eff[c] = len(als[c])
+            al[c, :len(als[c])] = als[c]
+            be[c, :len(bes[c])] = bes[c]
+        gn, Ms, r0s = (self._per_column(v, k, nm) for v, nm in ((gnorm, "gnorm"), (M, "M"), (r0, "r0")))
+        s = np.zeros((max(k, 1), m), dtype=np.float64)
+        infos = (_lib.CrnInfo * max(k, 1))()
+        dp = _lib._dp
+        call("krcn_cubic_tridiag_block", self._h, k, m, m_eff.ctypes.data_as(_lib._ip), al.ctypes.data_as(dp),
+             be.ctypes.data_as(dp), gn.ctypes.data_as(dp), Ms.ctypes.data_as(dp), r0s.ctypes.data_as(dp), float(eps),
+             int(it_max), s.ctypes.data_as(dp), infos, _stream(self.device))
+        return [s[c, :m_eff[c]].copy() for c in range(k)], [infos[c] for c in range(k)]
+
+    def crn_step_block(self, X, b, values, m, reg_coef, AX=None, V=None, active=None, tol=1e-6, l2=0.0, ls_beta=0.5,
+                       r0=0.1, solver_eps=1e-8, solver_it_max=100, max_trials=20, X_new=None, AX_new=None):
+        """One Krylov-CRN step of k problems over this matrix behind one library
+        call (krcn_crn_step_block): column c is `crn_step(X[:, c], b_c,
+        values[c], m, reg_coef[c], l2=l2[c], r0=r0[c])` with the line search
+        decided per column on the device.  X: (d, k) iterates; b: (n,) labels or
+        an (n, k) block; values: length-k f_c(x_c); reg_coef, l2, r0: floats or
+        length-k sequences; AX: X X when the caller has it; active: length-k
+        flags (a column with a false flag is copied through unchanged).  Returns
+        (X_new, AX_new, alphas, betas, infos): device (d, k) and (n, k) blocks,
+        the recurrences' alphas / betas as lanczos_block() returns them, and a
+        list of _lib.CrnInfo."""
+        m = int(m)
+        if m < 1:
+            raise ValueError("m must be >= 1")
+        k = int(self._check_block(X, self.d, None, "X").shape[1])
+        b_cols = self._labels(b, k)
+        if AX is not None:
+            self._check_block(AX, self.n, k, "AX")
+        vals = self._per_column(values, k, "values")
+        regs = self._per_column(reg_coef, k, "reg_coef")
+        l2s = self._per_column(l2, k, "l2")
+        r0s = self._per_column(r0, k, "r0")
+        act = None
+        if active is not None:
+            act = np.ascontiguousarray(np.asarray(active).reshape(-1) != 0, dtype=np.int32)
+            if len(act) != k:
+                raise ValueError(f"active must have one entry per column ({k}), got {len(act)}")
+        if V is None:
+            V = torch.empty((m, self.d, k), dtype=self.dtype, device=self.device)
+        elif (not isinstance(V, torch.Tensor) or V.dtype != self.dtype or V.device != self.device
+              or not V.is_contiguous() or tuple(V.shape) != (m, self.d, k)):
+            raise ValueError(f"V must be a contiguous ({m}, {self.d}, {k}) {self.dtype} tensor on {self.device}")
+        X_new = self._block_out(X_new, self.d, k)
+        AX_new = self._block_out(AX_new, self.n, k)
+        mb = max(m - 1, 1)
+        al = np.zeros((max(k, 1), m), dtype=np.float64)
+        be = np.zeros((max(k, 1), mb), dtype=np.float64)
+        infos = (_lib.CrnInfo * max(k, 1))()
+        dp = _lib._dp
+        call("krcn_crn_step_block", self._h, k, _ptr(X), _ptr(b), b_cols, _ptr(AX), vals.ctypes.data_as(dp),
+             None if act is None else act.ctypes.data_as(_lib._ip), m, float(tol), l2s.ctypes.data_as(dp),
+             regs.ctypes.data_as(dp), float(ls_beta), r0s.ctypes.data_as(dp), float(solver_eps), int(solver_it_max),
+             int(max_trials), _ptr(V), _ptr(X_new), _ptr(AX_new), al.ctypes.data_as(dp), be.ctypes.data_as(dp), infos,
+             _stream(self.device))
+        alphas = [al[c, :infos[c].lanczos.m_eff].copy() for c in range(k)]
+        betas = [be[c, :max(infos[c].lanczos.m_eff - 1, 0)].copy() for c in range(k)]
+        return X_new, AX_new, alphas, betas, [infos[c] for c in range(k)]
+
     # -- vector helpers ----------------------------------------------------
     def _space_len(self, space):
         return self.n if space == _lib.KRCN_SPACE_N else self.d

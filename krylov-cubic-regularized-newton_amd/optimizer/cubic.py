@@ -343,6 +343,123 @@ class Cubic_Krylov_LS(Optimizer):
         self.trace.solver_its.append(self.solver_it)
 
 
+class _BatchTrace:
+    """What Cubic_Krylov_LS_Batch.run records: one length-k array of loss values per step."""
+
+    def __init__(self):
+        self.values = []
+
+
+class Cubic_Krylov_LS_Batch:
+    """k Krylov-CRN problems over one design matrix, advanced together: one
+    krcn_crn_step_block call per step, column c being one step of
+    `Cubic_Krylov_LS(device_step=True)` on problem c (cubic.py:265-309) with the
+    line search decided per column on the device.
+
+    loss: an unsharded LogisticRegression (its matrix, dtype, default labels and
+    l2).  k: the number of problems.  B: None (every column uses the loss's
+    labels) or an (n, k) block of labels (one-vs-rest).  l2 (default: the
+    loss's) and reg_coef: a float or a length-k sequence.  subspace_dim,
+    solver_eps, beta, breakdown_tol as Cubic_Krylov_LS; tolerance > 0 makes a
+    column whose step length falls below it inactive (its iterate is kept).
+
+    After run(): xs (device (d, k)), values, reg_coefs, r0s, solver_its
+    (cumulative), its (steps each column took), trials (backtracking trials,
+    cumulative), active, and trace.values."""
+
+    def __init__(self, loss, k, B=None, l2=None, reg_coef=None, subspace_dim=10, solver_eps=1e-8, beta=0.5,
+                 breakdown_tol=1e-6, tolerance=0):
+        from krcn import _lib
+        from .loss import _labels01
+        if getattr(loss, "shard", None) is not None:
+            raise NotImplementedError("Cubic_Krylov_LS_Batch is implemented for unsharded problems")
+        k = int(k)
+        if not 1 <= k <= _lib.KRCN_BLOCK_MAX:
+            raise ValueError(f"k must lie in [1, {_lib.KRCN_BLOCK_MAX}], got {k}")
+        if reg_coef is None:
+            raise ValueError("reg_coef is required (a float or one per column)")
+        self.loss = loss
+        self.k = k
+        X = loss.device_matrix
+        if B is None:
+            self._b = loss._b_dev
+        else:
+            Bh = np.asarray(B)
+            if Bh.shape != (X.n, k):
+                raise ValueError(f"B must be an ({X.n}, {k}) block of labels, got shape {Bh.shape}")
+            Bh = np.stack([_labels01(Bh[:, c]) for c in range(k)], axis=1)
+            self._b = torch.from_numpy(np.ascontiguousarray(Bh, dtype=loss._np_dtype())).to(loss.device)
+        self.l2s = X._per_column(float(loss.l2) if l2 is None else l2, k, "l2")
+        self.reg_coefs = X._per_column(reg_coef, k, "reg_coef").copy()
+        self.subspace_dim = int(subspace_dim)
+        self.solver_eps = solver_eps
+        self.beta = beta
+        self.breakdown_tol = breakdown_tol
+        self.tolerance = tolerance
+        self.trace = _BatchTrace()
+        self.xs = None
+        self.values = None
+        self.last_infos = None
+        self._V = None
+
+    def _block(self, x0):
+        loss, k = self.loss, self.k
+        x0 = x0.detach().cpu().numpy() if isinstance(x0, torch.Tensor) else np.asarray(x0)
+        d = loss.device_matrix.d
+        if x0.shape == (d,):
+            x0 = np.repeat(x0[:, None], k, axis=1)
+        elif x0.shape != (d, k):
+            raise ValueError(f"x0 must have shape ({d},) or ({d}, {k}), got {x0.shape}")
+        return torch.from_numpy(np.ascontiguousarray(x0, dtype=loss._np_dtype())).to(loss.device)
+
+    def run(self, x0, it_max):
+        """At most it_max steps from x0 ((d,): every column starts there, or
+        (d, k)); ends early when no column is active.  Returns the trace."""
+        X, k, m = self.loss.device_matrix, self.k, self.subspace_dim
+        self.xs = self._block(x0)
+        AX = X.matvec_block(self.xs)
+        self.values = X.value_block(AX, self._b, self.xs, self.l2s).copy()
+        self.r0s = np.full(k, 0.1)
+        self.solver_its = np.zeros(k, dtype=np.int64)
+        self.its = np.zeros(k, dtype=np.int64)
+        self.trials = np.zeros(k, dtype=np.int64)
+        self.active = np.ones(k, dtype=bool)
+        self.trace = _BatchTrace()
+        if self._V is None or tuple(self._V.shape) != (m, X.d, k):
+            self._V = torch.empty((m, X.d, k), dtype=X.dtype, device=X.device)
+        spare = (torch.empty_like(self.xs), torch.empty_like(AX))
+        for _ in range(int(it_max)):
+            if not self.active.any():
+                break
+            X_new, AX_new, _, _, infos = X.crn_step_block(
+                self.xs, self._b, self.values, m, self.reg_coefs, AX=AX, V=self._V, active=self.active,
+                tol=self.breakdown_tol, l2=self.l2s, ls_beta=self.beta, r0=self.r0s, solver_eps=self.solver_eps,
+                max_trials=20, X_new=spare[0], AX_new=spare[1])
+            self.last_infos = infos
+            for c in range(k):
+                if not self.active[c]:
+                    continue
+                if infos[c].solver_status == 1:
+                    raise la.LinAlgError(f"column {c}: T + lam I is not positive definite")
+                if infos[c].solver_status == 2:
+                    raise ArithmeticError(f"column {c}: cubic subproblem: the derivative of phi was zero")
+            spare, self.xs, AX = (self.xs, AX), X_new, AX_new
+            for c in range(k):
+                if not self.active[c]:
+                    continue
+                info = infos[c]
+                self.values[c] = info.value_new
+                self.reg_coefs[c] = info.reg_coef
+                self.r0s[c] = info.lam
+                self.solver_its[c] += info.solver_it
+                self.its[c] += 1
+                self.trials[c] += info.trials
+                if self.tolerance > 0 and info.dx_norm < self.tolerance:
+                    self.active[c] = False
+            self.trace.values.append(self.values.copy())
+        return self.trace
+
+
 class Cubic_LS(Optimizer):
     """Full-space cubic regularized Newton with line search (cubic.py:115-235;
     Nesterov & Polyak 2006), on the device kernels.
