@@ -627,6 +627,69 @@ krcn_status krcn_crn_step(krcn_csr* h, const void* x, const void* b, const void*
                           void* x_new, void* Ax_new, double* alphas_host, double* betas_host,
                           krcn_crn_info* info_host, void* stream);
 
+/* ---- the SSCN step on the device ------------------------------------------ */
+/* Largest coordinate block of krcn_cubic_dense / krcn_sscn_step (the reference
+ * driver's default subspace_dim is 100). */
+enum { KRCN_SSCN_MAX = 128 };
+
+/* SYNCHRONOUS.  argmin_s <g,s> + 1/2 s^T H s + M/3 ||s||^3 for a symmetric
+ * k x k H (HOST, row-major k * k; only the upper triangle, column >= row, is
+ * read, as by the host's solve(assume_a='pos')) and a general g (k HOST
+ * doubles), 1 <= k <= KRCN_SSCN_MAX.  Solved by one workgroup on the device in
+ * fp64 whatever the handle's dtype: scipy's scalar
+ * Newton (root_scalar, method="newton", x0 = r0, xtol = eps, maxiter = it_max)
+ * on phi(lam) = lam^2 - M^2 ||s(lam)||^2 — the loop krcn_cubic_tridiag runs —,
+ * one Cholesky factorisation of H + lam I per lam shared by phi and dphi (a
+ * pivot <= 0 or non-finite is solver_status 1, the host's LinAlgError from
+ * solve(assume_a='pos')), two substitution pairs per lam, fixed-order sums and
+ * the reference's closing expressions.  Fills the solver fields of info_host
+ * (solver_it, solver_status, reg_coef, lam, model_decrease) and zeroes the
+ * rest; s_host receives the k entries of s (zeros when the solve failed:
+ * solver_status 1 or 2).  Argument errors (null handle or pointer, k outside
+ * the range, it_max < 1) are KRCN_ERR_INVALID before any HIP call.  Uses the
+ * coordinate workspace and the step workspace (allocated on first use).
+ * Replaces cubic_solver_root (dense branch), cubic.py:40-75, as SSCN calls it
+ * (cubic.py:373-374, :386-387). */
+krcn_status krcn_cubic_dense(krcn_csr* h, int k, const double* H_host, const double* g_host, double M,
+                             double r0, double eps, int it_max, double* s_host,
+                             krcn_crn_info* info_host, void* stream);
+
+/* SYNCHRONOUS.  One SSCN step from x with f(x) = value over the k DISTINCT
+ * columns cols_host (HOST int32, 1 <= k <= KRCN_SSCN_MAX): Ax = X x if Ax is
+ * NULL, the coordinate gradient and the coordinate Hessian block
+ * (krcn_coord_gradient's and krcn_coord_hessian's kernels; their results stay
+ * on the device), x_new = x (one D2D copy), then the line search:
+ * M = max(reg_coef * ls_beta, DBL_EPSILON), trial 0, and while
+ * value_new > value - model_decrease and trials < max_trials: M /= ls_beta and
+ * the next trial.  A trial is the subproblem of krcn_cubic_dense over the block
+ * in selection order with l2 on its diagonal (every trial starts from the
+ * caller's r0), x_new[c_a] = x[c_a] + s_a, Ax_new = Ax + X[:, cols] s
+ * (krcn_coord_update's walk; every trial starts from the same Ax),
+ * f(x_new) = mean + l2 / 2 * ||x_new||^2 from krcn_loss_mean's and
+ * krcn_diff_norm's partial sums in their order, and the test; the decision is
+ * taken on the device and the launches of later trials are guarded by it, so
+ * x_new / Ax_new hold the accepted trial (the last one at the cap).  The host
+ * enqueues trials 0 and 1, then batches of four, synchronises once per batch
+ * and never before the first batch ends.  A failed solve (solver_status 1 or
+ * 2) ends the chain; x_new and Ax_new are then unspecified.  info_host: the
+ * fields of krcn_crn_step, with dx_norm the solver's ||s|| and `lanczos`
+ * zeroed.  x_new (d) and Ax_new (n) alias no input.
+ * Refused with KRCN_ERR_INVALID before any launch, the position named: an
+ * index outside [0, d), a repeated index, k outside [1, KRCN_SSCN_MAX];
+ * sharded handles get KRCN_ERR_UNSUPPORTED.  n == 0 or nnz == 0: the model is
+ * the l2 term alone (gradient l2 x_I, Hessian l2 I, Ax_new a copy of Ax), as
+ * in the coordinate calls; with n == 0 the mean over no rows counts as 0, so
+ * value_new = l2 / 2 * ||x_new||^2 (b, Ax and Ax_new may then be NULL).  Workspace: the coordinate workspace, the step
+ * workspace of krcn_crn_step and 2,560 bytes of its own, all in the owner table
+ * and counted by krcn_csr_owned_bytes; a second step with the same k allocates
+ * nothing.  Builds pass plans only when Ax is NULL (before any scratch buffer
+ * is read: the build may move them).
+ * Replaces the body of SSCN.step, cubic.py:352-398. */
+krcn_status krcn_sscn_step(krcn_csr* h, int k, const int32_t* cols_host, const void* x, const void* b,
+                           const void* Ax, double value, double l2, double reg_coef, double ls_beta,
+                           double r0, double solver_eps, int solver_it_max, int max_trials, void* x_new,
+                           void* Ax_new, krcn_crn_info* info_host, void* stream);
+
 /* ---- the batched Krylov-CRN step: k problems over one X per call ---------- */
 /* The batch forms of krcn_gradient, the loss value, krcn_cubic_tridiag and
  * krcn_crn_step over the (L, k) blocks of the block products (element (i, c)

@@ -4,39 +4,12 @@
 // The entry points validate the selection on the host before anything is
 // launched, read h->tptr / tidx / tval at call time (never cached: the
 // placement code may move buffers), need no pass plans and use a workspace of
-// their own (CoordWs), not the handle's u / tn / W / td.
+// their own (CoordWs, krcn_coord_ws.hpp), not the handle's u / tn / W / td.
 #include "krcn_internal.hpp"
 #include "krcn_coord.hpp"
+#include "krcn_coord_ws.hpp"
 
 using namespace krcn;
-
-// The coordinate workspace for selections of up to cap columns (cap = k rounded
-// up to a multiple of 64; grown when k grows).
-//   device  delta (cap doubles) | cols (cap int32) | result (cap x cap doubles)
-//           = cap (12 + 8 cap) bytes, one block of the handle's owner table
-//   pinned  the result's host mirror | kCoordSlots staging slots (delta | cols)
-// Staging: a call copies cols_host / delta_host into the next slot of the ring
-// (a host memcpy, so the caller may overwrite its arrays once the call
-// returns), enqueues one H2D copy from that slot and records the slot's event
-// behind it; a slot is refilled only after its event has completed, so a copy
-// still in flight never reads a slot the next call is writing.  The device
-// side needs no ring: copies and kernels of one handle share one stream.
-constexpr int kCoordSlots = 4;
-struct CoordWs {
-  int cap = 0;
-  char* dev = nullptr;
-  double* delta = nullptr;
-  int* cols = nullptr;
-  double* res = nullptr;
-  char* pin = nullptr;
-  double* res_host = nullptr;
-  char* slot[kCoordSlots] = {};
-  hipEvent_t ev[kCoordSlots] = {};
-  bool busy[kCoordSlots] = {};
-  int next = 0;
-};
-
-static size_t coord_slot_bytes(int cap) { return size_t(cap) * 12; }
 
 static void coord_release(krcn_csr* h) {
   CoordWs* w = h->cw;
@@ -51,7 +24,7 @@ static void coord_release(krcn_csr* h) {
 
 void coord_free(krcn_csr* h) { coord_release(h); }
 
-static krcn_status coord_reserve(krcn_csr* h, int k, hipStream_t s) {
+krcn_status coord_reserve(krcn_csr* h, int k, hipStream_t s) {
   if (h->cw && h->cw->cap >= k) return KRCN_OK;
   const int cap = (k + 63) / 64 * 64;
   if (h->cw) {
@@ -72,6 +45,21 @@ static krcn_status coord_reserve(krcn_csr* h, int k, hipStream_t s) {
     HIPCHK(hipEventCreateWithFlags(&w->ev[i], hipEventDisableTiming));
   }
   w->cap = cap;   // (last: a failed build leaves cap = 0 and is rebuilt by the next call)
+  return KRCN_OK;
+}
+
+krcn_status coord_stage_bytes(krcn_csr* h, const void* src, size_t bytes, void* dst, hipStream_t s) {
+  CoordWs* w = h->cw;
+  if (!w || bytes > coord_slot_bytes(w->cap))
+    return fail(KRCN_ERR_INVALID, "coord_stage_bytes: %zu bytes do not fit a staging slot of %zu", bytes,
+                w ? coord_slot_bytes(w->cap) : size_t(0));
+  const int i = w->next;
+  if (w->busy[i]) HIPCHK(hipEventSynchronize(w->ev[i]));
+  std::memcpy(w->slot[i], src, bytes);
+  HIPCHK(hipMemcpyAsync(dst, w->slot[i], bytes, hipMemcpyHostToDevice, s));
+  HIPCHK(hipEventRecord(w->ev[i], s));
+  w->busy[i] = true;
+  w->next = (i + 1) % kCoordSlots;
   return KRCN_OK;
 }
 
@@ -110,8 +98,6 @@ static krcn_status coord_check(const char* fn, const krcn_csr* h, int k, const i
                   (long long)h->d);
   return KRCN_OK;
 }
-
-static bool coord_empty(const krcn_csr* h) { return h->n == 0 || h->nnz == 0; }
 
 extern "C" krcn_status krcn_csr_set_coord_window(krcn_csr* h, int rows) {
   if (!h) return fail(KRCN_ERR_INVALID, "krcn_csr_set_coord_window: null handle");
@@ -224,7 +210,8 @@ static krcn_status coord_update_impl(krcn_csr* h, int k, const int32_t* cols_hos
   const int grid = int((waves + kCoordUpdWaves - 1) / kCoordUpdWaves);
   const size_t lds = size_t(kCoordUpdWaves) * (size_t(Rw) + size_t(k)) * sizeof(double);   // <= 64 KiB
   hipLaunchKernelGGL((k_coord_update<T>), dim3(grid), dim3(kCoordUpdNT), lds, s, int(h->n), Rw, k, w->cols,
-                     w->delta, h->tptr, h->tidx, static_cast<const T*>(h->tval), Ax_in, Ax_out);
+                     w->delta, h->tptr, h->tidx, static_cast<const T*>(h->tval), Ax_in, Ax_out,
+                     static_cast<const int*>(nullptr));
   LAUNCHCHK();
   return KRCN_OK;
 }

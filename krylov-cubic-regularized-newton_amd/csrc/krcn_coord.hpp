@@ -174,13 +174,18 @@ __global__ __launch_bounds__(kCoordHessNT) void k_coord_hess(int nrows, int R, i
 // Ax_out = Ax_in + X[:, cols] delta, column by column in the order of cols.
 // Dynamic LDS per wave: Rw doubles (the window), then k column starts and k
 // column counts inside the window.
-template <typename T>
+// kGuard (the SSCN step's trials, krcn_sscn.hip): the launch returns at once
+// when *done is set, and delta was written by the launch before it.
+template <typename T, bool kGuard = false>
 __global__ __launch_bounds__(kCoordUpdNT) void k_coord_update(int n, int Rw, int k, const int* __restrict__ cols,
                                                               const double* __restrict__ delta,
                                                               const int* __restrict__ tptr,
                                                               const int* __restrict__ tidx,
                                                               const T* __restrict__ tval, const T* Ax_in,
-                                                              T* Ax_out) {
+                                                              T* Ax_out, const int* __restrict__ done) {
+  if constexpr (kGuard) {
+    if (*done) return;
+  }
   extern __shared__ double coord_dyn[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t r0l = (int64_t(blockIdx.x) * kCoordUpdWaves + wave) * Rw;

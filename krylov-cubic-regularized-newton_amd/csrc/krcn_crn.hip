@@ -11,12 +11,6 @@ static_assert(kCubicMaxM == kLzMaxM, "the subproblem kernel's LDS vectors hold t
 
 namespace {
 
-// Trials per submission: the first holds trials 0 and 1, every later one
-// kCrnBatch (a guarded trial that finds done set costs its
-// launches only, a host round trip costs a synchronisation).
-constexpr int kCrnFirstBatch = 2;
-constexpr int kCrnBatch = 4;
-
 constexpr size_t kCrnStateDoubles = sizeof(CrnState) / sizeof(double);
 
 struct CrnWs {
@@ -29,14 +23,6 @@ CrnWs crn_ws(const krcn_csr* h) {
   double* v = h->crn_ws + kCrnStateDoubles;
   return CrnWs{reinterpret_cast<CrnState*>(h->crn_ws), v, v + kLzMaxM, v + 2 * size_t(kLzMaxM),
                reinterpret_cast<CrnState*>(h->crn_res_dev)};
-}
-
-void solver_fields(const CrnState& st, krcn_crn_info* info) {
-  info->solver_it = st.solver_it;
-  info->solver_status = st.solver_status;
-  info->reg_coef = st.M;
-  info->lam = st.lam;
-  info->model_decrease = st.model_decrease;
 }
 
 struct StepArgs {
@@ -116,7 +102,7 @@ krcn_status crn_step_impl(krcn_csr* h, const T* x, const T* b, const T* Ax, cons
   if (!alphas_host || !betas_host) al_tmp.resize(2 * size_t(a.m));
   lanczos_results(h, a.m, alphas_host ? alphas_host : al_tmp.data(),
                   betas_host ? betas_host : (a.m > 1 ? al_tmp.data() + a.m : &be1), &info->lanczos);
-  solver_fields(st, info);
+  crn_solver_fields(st, info);
   info->accepted = st.accepted;
   info->trials = st.trials;
   info->value_new = st.value_new;
@@ -164,7 +150,7 @@ extern "C" krcn_status krcn_cubic_tridiag(krcn_csr* h, int m, const double* alph
     HIPCHK(hipStreamSynchronize(s));
     CrnState st;
     std::memcpy(&st, h->crn_res, sizeof(CrnState));
-    solver_fields(st, info_host);
+    crn_solver_fields(st, info_host);
     const bool solved = st.solver_status == kCubicOk || st.solver_status == kCubicItMax;
     for (int i = 0; i < m; ++i) s_host[i] = solved ? h->hostbuf[i] : 0.0;
     return KRCN_OK;

@@ -11,6 +11,7 @@
 #pragma once
 #include <cstddef>
 
+#include "krcn.h"
 #include "krcn_kernels.hpp"
 
 namespace krcn {
@@ -37,6 +38,22 @@ struct CrnState {
 };
 static_assert(offsetof(CrnState, done) == offsetof(LanczosState, done), "SrcGuard reads done");
 static_assert(sizeof(CrnState) % sizeof(double) == 0, "the state heads a block of doubles");
+
+// Trials per submission of a chain (krcn_crn_step, krcn_sscn_step): the first
+// holds trials 0 and 1, every later one kCrnBatch (a guarded
+// trial that finds done set costs its launches only, a host round trip costs a
+// synchronisation).
+constexpr int kCrnFirstBatch = 2;
+constexpr int kCrnBatch = 4;
+
+// The solver fields of a chain's record, as the host reads them back.
+inline void crn_solver_fields(const CrnState& st, krcn_crn_info* info) {
+  info->solver_it = st.solver_it;
+  info->solver_status = st.solver_status;
+  info->reg_coef = st.M;
+  info->lam = st.lam;
+  info->model_decrease = st.model_decrease;
+}
 
 // Start of a chain.  lz != nullptr: the block k_lz_final packed (state,
 // alphas[0..m), betas[0..m-1)) becomes the subproblem's input, with the
@@ -165,13 +182,87 @@ __device__ __forceinline__ void cubic_backward(int m, const double* e, double* b
   }
 }
 
+struct CubicSolve {
+  int its, status;
+  double root, dec;
+  double ns;   // ||s|| of the closing solve (0 when it failed)
+};
+
+// The scalar Newton loop of the cubic subproblem, shared by the tridiagonal
+// kernels (cubic_tridiag_solve) and the dense one (krcn_cubic_dense.hpp):
+// scipy's newton() on phi(lam) = lam^2 - M^2 ||s(lam)||^2 from r0 (fval == 0
+// returns p0, fder == 0 is an error, p = p0 - fval / fder, converged when
+// |p - p0| <= eps, at most it_max iterations and then the last p with "not
+// converged"), and the host's closing expressions.  The caller supplies the
+// linear algebra over y = (H + lam I)^{-1} g = -s(lam) (negation is exact and
+// the solves are odd, so phi, dphi and s have the host expressions' values):
+//   solve_g(lam)  factor H + lam I and solve for y; false: not positive definite
+//   solve_y()     z = (H + lam I)^{-1} y with the factorisation solve_g left
+//   dot_yy / dot_yz   the block's fixed-order sums
+//   g_dot_s()     np.dot(g, s) of the closing solve
+//   store_s()     writes s = -y out
+// Every thread of the workgroup calls it with the same arguments and gets the
+// same result; the loop is bounded by it_max.
+template <class SolveG, class SolveY, class DotYY, class DotYZ, class GDotS, class StoreS>
+__device__ __forceinline__ CubicSolve cubic_newton(double M, double r0, double eps, int it_max, SolveG&& solve_g,
+                                                   SolveY&& solve_y, DotYY&& dot_yy, DotYZ&& dot_yz,
+                                                   GDotS&& g_dot_s, StoreS&& store_s) {
+  int status = kCubicOk, its = 0;
+  double p0 = r0, root = r0;
+  bool found = false;
+  const double M2 = M * M;
+  for (int itr = 0; itr < it_max; ++itr) {
+    if (!solve_g(p0)) {
+      status = kCubicNotPd;
+      break;
+    }
+    const double nrm = sqrt(dot_yy());
+    const double fval = p0 * p0 - M2 * (nrm * nrm);
+    if (fval == 0.0) {
+      root = p0;
+      its = itr;
+      found = true;
+      break;
+    }
+    solve_y();
+    const double dnorm2 = -2.0 * dot_yz();
+    const double fder = 2.0 * p0 - M2 * dnorm2;
+    if (fder == 0.0) {
+      root = p0;
+      its = itr + 1;
+      status = kCubicDerZero;
+      break;
+    }
+    const double p = p0 - fval / fder;
+    its = itr + 1;
+    root = p;
+    if (p == p0 || fabs(p - p0) <= eps) {
+      found = true;
+      break;
+    }
+    p0 = p;
+  }
+  if (status == kCubicOk && !found) status = kCubicItMax;   // the last p is the root, as root_scalar returns it
+
+  double dec = 0.0, ns = 0.0;
+  if (status == kCubicOk || status == kCubicItMax) {
+    if (!solve_g(root)) {
+      status = kCubicNotPd;
+    } else {
+      ns = sqrt(dot_yy());
+      const double gs = g_dot_s();
+      dec = root / 2.0 * (ns * ns) - M / 3.0 * (ns * ns * ns) - gs / 2.0;
+      store_s();
+    }
+  }
+  return CubicSolve{its, status, root, dec, ns};
+}
+
 // The tridiagonal cubic subproblem argmin_s <g,s> + 1/2 s^T T s + M/3 ||s||^3,
 // T = tridiag(be, al, be), g = gnorm e1 (cubic_solver_root_tridiag): scipy's
-// scalar Newton on phi(lam) = lam^2 - M^2 ||s(lam)||^2 from r0 (newton():
-// fval == 0 returns p0, fder == 0 is an error, p = p0 - fval / fder, converged
-// when |p - p0| <= eps, at most it_max iterations and then the last p with
-// "not converged"), one LDL^T per lam shared by phi and dphi, and the host's
-// closing expressions.  One workgroup; the recurrences run on thread 0 over
+// scalar Newton on phi(lam) = lam^2 - M^2 ||s(lam)||^2 from r0 (cubic_newton
+// above), one LDL^T per lam shared by phi and dphi, and the host's closing
+// expressions.  One workgroup; the recurrences run on thread 0 over
 // LDS, the elementwise divisions and the sums on all threads.  Works with
 // y = (T + lam I)^{-1} g = -s(lam): negation is exact and the solves are odd,
 // so phi, dphi and s have the host expressions' values.
@@ -180,10 +271,6 @@ __device__ __forceinline__ void cubic_backward(int m, const double* e, double* b
 // the same arguments and gets the same result): k_cubic_tridiag runs it on the
 // single chain's state, k_crnb_solve (krcn_crnb.hpp) on one column per
 // workgroup.  s_g receives the m entries of s when the solve succeeded.
-struct CubicSolve {
-  int its, status;
-  double root, dec;
-};
 __device__ __forceinline__ CubicSolve cubic_tridiag_solve(int m, double M, double gnorm,
                                                           const double* __restrict__ al_g,
                                                           const double* __restrict__ be_g,
@@ -236,55 +323,12 @@ __device__ __forceinline__ CubicSolve cubic_tridiag_solve(int m, double M, doubl
     return block_sum(acc, sm);
   };
 
-  int status = kCubicOk, its = 0;
-  double p0 = r0, root = r0;
-  bool found = false;
-  const double M2 = M * M;
-  for (int itr = 0; itr < it_max; ++itr) {
-    if (!solve_g(p0)) {
-      status = kCubicNotPd;
-      break;
-    }
-    const double nrm = sqrt(dot(y, y));
-    const double fval = p0 * p0 - M2 * (nrm * nrm);
-    if (fval == 0.0) {
-      root = p0;
-      its = itr;
-      found = true;
-      break;
-    }
-    solve_y();
-    const double dnorm2 = -2.0 * dot(y, z);
-    const double fder = 2.0 * p0 - M2 * dnorm2;
-    if (fder == 0.0) {
-      root = p0;
-      its = itr + 1;
-      status = kCubicDerZero;
-      break;
-    }
-    const double p = p0 - fval / fder;
-    its = itr + 1;
-    root = p;
-    if (p == p0 || fabs(p - p0) <= eps) {
-      found = true;
-      break;
-    }
-    p0 = p;
-  }
-  if (status == kCubicOk && !found) status = kCubicItMax;   // the last p is the root, as root_scalar returns it
-
-  double dec = 0.0;
-  if (status == kCubicOk || status == kCubicItMax) {
-    if (!solve_g(root)) {
-      status = kCubicNotPd;
-    } else {
-      const double ns = sqrt(dot(y, y));
-      const double gs = gnorm * (0.0 - y[0]);   // np.dot(g, s): g = gnorm e1, s = -y
-      dec = root / 2.0 * (ns * ns) - M / 3.0 * (ns * ns * ns) - gs / 2.0;
-      for (int i = tid; i < m; i += kNT) s_g[i] = 0.0 - y[i];
-    }
-  }
-  return CubicSolve{its, status, root, dec};
+  return cubic_newton(
+      M, r0, eps, it_max, solve_g, solve_y, [&]() { return dot(y, y); }, [&]() { return dot(y, z); },
+      [&]() { return gnorm * (0.0 - y[0]); },   // np.dot(g, s): g = gnorm e1, s = -y
+      [&]() {
+        for (int i = tid; i < m; i += kNT) s_g[i] = 0.0 - y[i];
+      });
 }
 
 [[maybe_unused]] static __global__ __launch_bounds__(kNT) void k_cubic_tridiag(CrnState* st,

@@ -11,6 +11,7 @@
 //   krcn_lanczos_block.hip  the batched Lanczos: k recurrences in lockstep over the block HVP (krcn_blz.hpp;
 //                        its per-column state rule, krcn_blz_state.hpp, is host-only like the three below)
 //   krcn_crn.hip         the device cubic subproblem and the one-call Krylov-CRN step (krcn_cubic.hpp)
+//   krcn_sscn.hip        the dense cubic subproblem and the one-call SSCN step (krcn_cubic_dense.hpp)
 //   krcn_lanczos_f64.hip / krcn_lanczos_f32.hip
 //                        the device Lanczos recurrence (krcn_lanczos_impl.hpp), one dtype each
 // Three host-only headers (plain C++17, no HIP header: they also build with g++
@@ -339,6 +340,8 @@ struct krcn_csr {
   double* crn_res_dev = nullptr;
   CoordWs* cw = nullptr;      // coordinate workspace (first krcn_coord_* call; its device block is in own)
   int coord_window = 0;       // krcn_csr_set_coord_window (0: auto)
+  char* sscn_ws = nullptr;    // krcn_sscn_step: the selection in both orders, its permutation and the
+                              //   coordinate gradient (krcn_sscn.hip; a fixed block, allocated by the first step)
   void* blk_u = nullptr;      // krcn_hvp_block: its (n, blk_k) intermediate (krcn_block.hip; grown when k grows)
   int blk_k = 0;
   int* blk_long[2] = {};      // block products: rows of X / X^T above KRCN_BLOCK_LONG_ROW, listed at the

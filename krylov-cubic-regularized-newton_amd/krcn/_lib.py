@@ -30,6 +30,7 @@ KRCN_PLAN_JAG, KRCN_PLAN_DENSE = 5, 6
 KRCN_SPACE_N, KRCN_SPACE_D = 0, 1
 KRCN_COORD_MAX = 1024
 KRCN_BLOCK_MAX, KRCN_BLOCK_LONG_ROW = 16, 512
+KRCN_SSCN_MAX = 128
 
 _STATUS_NAMES = {1: "KRCN_ERR_INVALID", 2: "KRCN_ERR_HIP", 3: "KRCN_ERR_RCCL",
                  4: "KRCN_ERR_UNSUPPORTED"}
@@ -126,6 +127,9 @@ SIGNATURES = {
     "krcn_cubic_tridiag": [_vp, _i, _dp, _dp, _d, _d, _d, _d, _i, _dp, ctypes.POINTER(CrnInfo), _vp],
     "krcn_crn_step": [_vp, _vp, _vp, _vp, _d, _i, _i, _d, _d, _d, _d, _d, _d, _i, _i, _vp, _vp, _vp, _dp, _dp,
                       ctypes.POINTER(CrnInfo), _vp],
+    "krcn_cubic_dense": [_vp, _i, _dp, _dp, _d, _d, _d, _i, _dp, ctypes.POINTER(CrnInfo), _vp],
+    "krcn_sscn_step": [_vp, _i, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _d, _d, _i, _i, _vp, _vp,
+                       ctypes.POINTER(CrnInfo), _vp],
     "krcn_gradient_block": [_vp, _i, _vp, _vp, _i, _vp, _dp, _vp, _vp],
     "krcn_value_block": [_vp, _i, _vp, _vp, _i, _vp, _dp, _dp, _vp],
     "krcn_cubic_tridiag_block": [_vp, _i, _i, _ip, _dp, _dp, _dp, _dp, _dp, _d, _i, _dp, ctypes.POINTER(CrnInfo), _vp],

@@ -590,6 +590,48 @@ class DeviceCSR:
         me = info.lanczos.m_eff
         return x_new, Ax_new, al[:me], be[:max(me - 1, 0)], info
 
+    # -- the SSCN step on the device -------------------------------------------
+    def cubic_dense(self, H, g, M, r0=0.1, eps=1e-8, it_max=100):
+        """The cubic subproblem over a dense symmetric k x k block H and a
+        general g, 1 <= k <= KRCN_SSCN_MAX, solved on the device in fp64
+        (krcn_cubic_dense; what optimizer.cubic.cubic_solver_root computes on
+        the host).  Only the upper triangle of H is read.  Returns (s, info) as
+        `cubic_tridiag`: status 1 means H + lam I was not positive definite."""
+        Hd = np.ascontiguousarray(H.toarray() if hasattr(H, "toarray") else H, dtype=np.float64)
+        gd = np.ascontiguousarray(g, dtype=np.float64).reshape(-1)
+        k = len(gd)
+        if Hd.shape != (k, k):
+            raise ValueError(f"H must be ({k}, {k}), got {Hd.shape}")
+        s = np.zeros(max(k, 1), dtype=np.float64)
+        info = _lib.CrnInfo()
+        call("krcn_cubic_dense", self._h, k, Hd.ctypes.data_as(_lib._dp), gd.ctypes.data_as(_lib._dp), float(M),
+             float(r0), float(eps), int(it_max), s.ctypes.data_as(_lib._dp), ctypes.byref(info),
+             _stream(self.device))
+        return s[:k], info
+
+    def sscn_step(self, cols, x, b, value, reg_coef, Ax=None, l2=0.0, ls_beta=0.5, r0=0.1,
+                  solver_eps=float(np.finfo(float).eps), solver_it_max=100, max_trials=20, x_new=None, Ax_new=None):
+        """One SSCN step from x with f(x) = value over the distinct columns
+        `cols` behind one library call (krcn_sscn_step): coordinate gradient
+        and Hessian block, then the backtracking line search with the dense
+        subproblem, the coordinate update of Ax and the accept / reject test
+        on the device.  Ax is X x when the caller has it.  Returns (x_new,
+        Ax_new, info): the iterate the step keeps, its product with X, and a
+        _lib.CrnInfo (accepted, trials, solver_it, solver_status, reg_coef,
+        lam, model_decrease, value_new, dx_norm = ||s||)."""
+        c, cp = self._selection(cols)
+        self._check(x, self.d, "x")
+        self._check(b, self.n, "b")
+        if Ax is not None:
+            self._check(Ax, self.n, "Ax")
+        x_new = self.empty_d() if x_new is None else self._check(x_new, self.d, "x_new")
+        Ax_new = self.empty_n() if Ax_new is None else self._check(Ax_new, self.n, "Ax_new")
+        info = _lib.CrnInfo()
+        call("krcn_sscn_step", self._h, len(c), cp, _ptr(x), _ptr(b), _ptr(Ax), float(value), float(l2),
+             float(reg_coef), float(ls_beta), float(r0), float(solver_eps), int(solver_it_max), int(max_trials),
+             _ptr(x_new), _ptr(Ax_new), ctypes.byref(info), _stream(self.device))
+        return x_new, Ax_new, info
+
     # -- the batched Krylov-CRN step: k problems over one X --------------------
     @staticmethod
     def _per_column(v, k, name):

@@ -594,10 +594,36 @@ class SSCN(Optimizer):
     Hanzely et al. 2020, §7.1), on the device kernels: the coordinate gradient
     and Hessian (loss.partial_gradient / partial_hessian), the coordinate
     update of x and the incremental Ax update (loss.update_mat_vec_product)
-    run on the GPU; the m x m subproblem on the host, as in the reference."""
+    run on the GPU; the m x m subproblem on the host, as in the reference.
 
-    def __init__(self, reg_coef=None, subspace_dim=100, solver_eps=1e-8, beta=0.5, *args, **kwargs):
+    device_step=True (not in the reference; off by default) runs the whole step
+    behind one krcn_sscn_step call instead: the gradient and the Hessian block
+    stay on the device, the dense subproblem is solved there in one workgroup
+    and the line search's decision is taken by a device kernel, with the trials
+    enqueued in guarded batches (unsharded losses, subspace_dim <=
+    KRCN_SSCN_MAX = 128, at most 20 backtracking trials).  The rng draw is the
+    host path's.  Differences: self.grad and self.hess are not brought back
+    (the step does not set them), and the loss's f_opt / x_opt follow the iterate each step
+    keeps, not the rejected trials, whose vectors are overwritten on the
+    device.  The host loop backtracks without a cap; the device step stops
+    after 20 rejected trials and keeps the last one, as Cubic_Krylov_LS does:
+    that step warns (RuntimeWarning) and is counted in `capped_steps`.
+    `last_trials` holds the backtracking trials of the last step on both
+    paths."""
+
+    def __init__(self, reg_coef=None, subspace_dim=100, solver_eps=1e-8, beta=0.5, *args, device_step=False,
+                 **kwargs):
         super().__init__(*args, **kwargs)
+        if device_step:
+            from krcn import _lib
+            if getattr(self.loss, "shard", None) is not None:
+                raise NotImplementedError("device_step=True is implemented for unsharded problems")
+            if not 1 <= int(subspace_dim) <= _lib.KRCN_SSCN_MAX:
+                raise ValueError(f"device_step=True needs 1 <= subspace_dim <= {_lib.KRCN_SSCN_MAX}, "
+                                 f"got {subspace_dim}")
+        self.device_step = bool(device_step)
+        self.last_trials = 0
+        self.capped_steps = 0       # device steps that ended at the trial cap without an accepted trial
         self.reg_coef = reg_coef
         self.solver_it = 0
         self.subspace_dim = subspace_dim
@@ -619,6 +645,8 @@ class SSCN(Optimizer):
 
     def step(self):
         """cubic.py:349-399."""
+        if self.device_step:
+            return self._step_on_device()
         loss = self.loss
         if self.value is None:
             self.value = loss.value(self.x)
@@ -633,6 +661,7 @@ class SSCN(Optimizer):
         x_new = self._coordinate_step(I_dev, s_new_sub)
         loss.update_mat_vec_product(Ax, s_new_sub, I)
         value_new = loss.value(x_new)
+        trials = 0
         while value_new > self.value - model_decrease:
             reg_coef = reg_coef / self.beta
             s_new_sub, solver_it, r0_new, model_decrease = cubic_solver_root(
@@ -640,11 +669,42 @@ class SSCN(Optimizer):
             x_new = self._coordinate_step(I_dev, s_new_sub)
             loss.update_mat_vec_product(Ax, s_new_sub, I)
             value_new = loss.value(x_new)
+            trials += 1
+        self.last_trials = trials
         self.x = x_new
         self.reg_coef = reg_coef
         self.value = value_new
         self.r0 = r0_new
         self.solver_it += solver_it
+
+    def _step_on_device(self):
+        """The same step as one krcn_sscn_step call: the state afterwards is
+        the host path's x, reg_coef, value, r0 and solver_it, and the loss's
+        cache holds X x_new for the new iterate."""
+        loss = self.loss
+        X = loss.device_matrix
+        if self.value is None:
+            self.value = loss.value(self.x)
+        I = self.rng.choice(self.dim, size=self.subspace_dim, replace=False)
+        x_new, Ax_new, info = X.sscn_step(
+            I, self.x, loss._b_dev, self.value, self.reg_coef, Ax=loss._device_Ax(self.x), l2=float(loss.l2),
+            ls_beta=self.beta, r0=self.r0, solver_eps=np.finfo(float).eps, max_trials=20)
+        if info.solver_status == 1:
+            raise la.LinAlgError("H + lam I is not positive definite")
+        if info.solver_status == 2:
+            raise ArithmeticError("cubic subproblem: the derivative of phi was zero")
+        if not info.accepted:
+            self.capped_steps += 1
+            warnings.warn(f"SSCN device step: no trial met the decrease test within {info.trials} backtracking "
+                          f"trials (reg_coef {info.reg_coef:.3e}); the last trial is kept", RuntimeWarning)
+        loss.adopt_product(x_new, Ax_new)
+        loss.note_value(x_new, info.value_new)
+        self.x = x_new
+        self.reg_coef = info.reg_coef
+        self.value = info.value_new
+        self.r0 = info.lam
+        self.solver_it += info.solver_it
+        self.last_trials = info.trials
 
     def init_run(self, *args, **kwargs):
         super().init_run(*args, **kwargs)
