@@ -22,7 +22,8 @@
  *     partials (krcn_csr_reserve, krcn_csr_attach_comm of a multi-rank
  *     communicator, the plan queries, or the first compute call of any other
  *     handle), in krcn_csr_reserve(.., reorth = 1) (CGS2 workspace) and in the
- *     first krcn_cg_solve, and the workspace of krcn_crn_step / krcn_cubic_tridiag
+ *     first krcn_cg_solve (the first krcn_cubic_cg allocates the same vectors,
+ *     one more d-vector and 16,512 bytes), and the workspace of krcn_crn_step / krcn_cubic_tridiag
  *     (about 50 KB) in krcn_csr_reserve of an unsharded handle or the first of
  *     those calls.  krcn_lanczos allocates nothing on a handle that is
  *     reserved for its m.  The coordinate calls (krcn_coord_*) allocate their
@@ -689,6 +690,52 @@ krcn_status krcn_sscn_step(krcn_csr* h, int k, const int32_t* cols_host, const v
                            const void* Ax, double value, double l2, double reg_coef, double ls_beta,
                            double r0, double solver_eps, int solver_it_max, int max_trials, void* x_new,
                            void* Ax_new, krcn_crn_info* info_host, void* stream);
+
+/* ---- the full-space cubic subproblem on the device: Newton over CG -------- */
+/* Result record of krcn_cubic_cg. */
+typedef struct {
+  int solver_it, solver_status;      /* as krcn_crn_info; status 4: a non-finite lam, rho or p.q ended the chain */
+  int cg_solves, cg_unconverged;     /* solves run; solves that ended at cg_maxiter */
+  int64_t cg_iterations, ticks;      /* x-updates over all solves; ticks enqueued until the end was seen */
+  double reg_coef, lam, model_decrease, s_norm;
+} krcn_cubic_cg_info;
+
+/* SYNCHRONOUS.  argmin_s <g,s> + 1/2 s^T H s + M/3 ||s||^3 for
+ * H = X^T diag(w) X / n_global + l2 I, never formed: scipy's scalar Newton
+ * (root_scalar, method="newton", x0 = r0, xtol = eps, maxiter = it_max) on
+ * phi(lam) = lam^2 - M^2 ||s(lam)||^2 — the loop krcn_cubic_tridiag runs —
+ * with every (H + lam I)^{-1} applied by krcn_cg_solve's conjugate gradients
+ * (shift l2 + lam, rtol cg_rtol, at most cg_maxiter updates, 10 d when
+ * cg_maxiter <= 0): y = (H + lam I)^{-1} g for phi, z = (H + lam I)^{-1} y for
+ * its derivative, the closing solve at the root, s = -y, and the reference's
+ * closing expressions (s_norm = ||s||, krcn_diff_norm's bits; model_decrease
+ * with krcn_dot's g.s).  w is the n-vector of Hessian weights, g and s are
+ * d-vectors of the handle's dtype that do not alias; scalars, sums and the
+ * Newton iteration are double.
+ * The host enqueues ticks — one CG iteration (the launches of krcn_cg_solve's)
+ * and one single-workgroup turn that takes every decision on the device: has
+ * the solve ended, the Newton step, the next solve's shift and tolerance — in
+ * batches of 16, synchronises once per batch and reads one mapped record;
+ * launches after the end return at once.  A solve that stops at cg_maxiter is
+ * counted in cg_unconverged and its iterate used, as the host path does.
+ * solver_status: 0 ok; 1 p.q <= 0 with rho > 0 (H + lam I is not positive
+ * definite); 2 phi' = 0; 3 it_max reached (the last iterate is the root and
+ * the closing solve still runs, as root_scalar returns it); 4 a non-finite
+ * lam, rho or p.q.  Statuses 1, 2 and 4 end the chain with s zeroed.
+ * KRCN_ERR_INVALID before any HIP call, scalars first: it_max < 1,
+ * !(cg_rtol >= 0), M not positive and finite, !(eps >= 0), a null handle or
+ * pointer, s == g; sharded handles get KRCN_ERR_UNSUPPORTED; d == 0 returns
+ * KRCN_OK with info zeroed.  KRCN_ERR_HIP if the chain has not ended after
+ * (2 it_max + 1)(cg_maxiter + 1) ticks.
+ * Workspace: krcn_cg_solve's r | p | q, one more d-vector, a state block of
+ * 16,512 bytes (all in the owner table, counted by krcn_csr_owned_bytes) and a
+ * mapped host record, allocated by the first call; a second call allocates
+ * nothing.  Builds pass plans on first use, before any scratch buffer is read.
+ * Replaces the root_scalar loop of Cubic_LS.cubic_solver_root_CG,
+ * cubic.py:152-182. */
+krcn_status krcn_cubic_cg(krcn_csr* h, const void* w, const void* g, double l2, double M, double r0,
+                          double eps, int it_max, double cg_rtol, int cg_maxiter /* <= 0: 10 d */,
+                          void* s /* d-vector, out */, krcn_cubic_cg_info* info_host, void* stream);
 
 /* ---- the batched Krylov-CRN step: k problems over one X per call ---------- */
 /* The batch forms of krcn_gradient, the loss value, krcn_cubic_tridiag and

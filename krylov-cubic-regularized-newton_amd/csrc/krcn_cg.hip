@@ -4,16 +4,16 @@
 #include "krcn_cg.hpp"
 #include "krcn_internal.hpp"
 
-namespace {
-
-constexpr int kCgCheckEvery = 16;   // iterations between host reads of the done flag
-
 krcn_status ensure_cg_ws(krcn_csr* h) {
   if (h->cg_r) return KRCN_OK;
   CHK(h->own.alloc(&h->cg_r, std::max<size_t>(size_t(3) * size_t(h->d) * h->vs, 1)));
   CHK(dalloc(h, &h->cg_st, 1));
   return KRCN_OK;
 }
+
+namespace {
+
+constexpr int kCgCheckEvery = 16;   // iterations between host reads of the done flag
 
 template <typename T>
 krcn_status cg_impl(krcn_csr* h, const T* w, const T* b, double shift, double rtol, int maxiter, T* x,

@@ -18,8 +18,9 @@ namespace krcn {
 
 constexpr int kCubicMaxM = 2044;   // = kLzMaxM (krcn_internal.hpp static_asserts it)
 
-// Solver status of the subproblem (krcn_crn_info.solver_status).
-enum { kCubicOk = 0, kCubicNotPd = 1, kCubicDerZero = 2, kCubicItMax = 3 };
+// Solver status of the subproblem (krcn_crn_info.solver_status); kCubicNonFinite
+// is krcn_cubic_cg's alone (a non-finite lam, rho or p.q: krcn_cgn_state.hpp).
+enum { kCubicOk = 0, kCubicNotPd = 1, kCubicDerZero = 2, kCubicItMax = 3, kCubicNonFinite = 4 };
 
 struct CrnState {
   int done;            // shares its offset with LanczosState::done (SrcGuard reads it)

@@ -80,6 +80,7 @@ static krcn_status destroy_impl(krcn_csr* h) {
   if (h->hostbuf) (void)hipHostFree(h->hostbuf);
   if (h->hostres) (void)hipHostFree(h->hostres);
   if (h->crn_res) (void)hipHostFree(h->crn_res);
+  if (h->cgn_res) (void)hipHostFree(h->cgn_res);
   if (h->blz_host) (void)hipHostFree(h->blz_host);
   if (h->crnb_host) (void)hipHostFree(h->crnb_host);
   if (h->gexec) (void)hipGraphExecDestroy(h->gexec);

@@ -12,6 +12,8 @@
 //                        its per-column state rule, krcn_blz_state.hpp, is host-only like the three below)
 //   krcn_crn.hip         the device cubic subproblem and the one-call Krylov-CRN step (krcn_cubic.hpp)
 //   krcn_sscn.hip        the dense cubic subproblem and the one-call SSCN step (krcn_cubic_dense.hpp)
+//   krcn_cubic_cg.hip    the full-space cubic subproblem, Newton over CG in one call (krcn_cgn.hpp; its
+//                        state rule, krcn_cgn_state.hpp, is host-only like the three below)
 //   krcn_lanczos_f64.hip / krcn_lanczos_f32.hip
 //                        the device Lanczos recurrence (krcn_lanczos_impl.hpp), one dtype each
 // Three host-only headers (plain C++17, no HIP header: they also build with g++
@@ -334,6 +336,10 @@ struct krcn_csr {
   int reorth_m = 0;           // CGS2 workspace reserved for Lanczos m <= this (krcn_csr_reserve)
   void* cg_r = nullptr;       // CG vectors r | p | q (3 d-vectors, krcn_cg_solve)
   struct krcn::CgState* cg_st = nullptr;
+  void* cgn_z = nullptr;      // krcn_cubic_cg (krcn_cubic_cg.hip): the d-vector z of its solve_y phase
+  double* cgn_st = nullptr;   //   the chain state, then the two partial arrays of a turn's sums
+  double* cgn_res = nullptr;  //   pinned, mapped host record the turn that ends the chain writes
+  double* cgn_res_dev = nullptr;
   double* crn_ws = nullptr;   // krcn_crn_step / krcn_cubic_tridiag: the chain state, then the subproblem's
                               // alphas | betas | s (three kLzMaxM-vectors; its solves work in LDS)
   double* crn_res = nullptr;  //   pinned, mapped host record the judge kernel writes (krcn_crn.hip)
@@ -529,6 +535,9 @@ inline void lanczos_results(const krcn_csr* h, int m, double* alphas_host, doubl
 // The workspace of krcn_cubic_tridiag / krcn_crn_step (krcn_crn.hip): allocated
 // by krcn_csr_reserve and by the first of those calls.
 krcn_status ensure_crn_ws(krcn_csr* h);
+// The vectors r | p | q and the state of krcn_cg_solve (krcn_cg.hip): allocated by the
+// first krcn_cg_solve or krcn_cubic_cg, which runs its solves in the same vectors.
+krcn_status ensure_cg_ws(krcn_csr* h);
 
 // The batched Lanczos in two parts (krcn_lanczos_block.hip): the launches of a
 // call alone — arguments as krcn_lanczos_block's, already checked; no

@@ -63,6 +63,14 @@ class CrnInfo(ctypes.Structure):
                 ("dx_norm", ctypes.c_double), ("lanczos", LanczosInfo)]
 
 
+class CubicCgInfo(ctypes.Structure):
+    """krcn_cubic_cg_info (include/krcn.h)."""
+    _fields_ = [("solver_it", ctypes.c_int), ("solver_status", ctypes.c_int), ("cg_solves", ctypes.c_int),
+                ("cg_unconverged", ctypes.c_int), ("cg_iterations", ctypes.c_int64), ("ticks", ctypes.c_int64),
+                ("reg_coef", ctypes.c_double), ("lam", ctypes.c_double), ("model_decrease", ctypes.c_double),
+                ("s_norm", ctypes.c_double)]
+
+
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
 _i64 = ctypes.c_int64
@@ -130,6 +138,7 @@ SIGNATURES = {
     "krcn_cubic_dense": [_vp, _i, _dp, _dp, _d, _d, _d, _i, _dp, ctypes.POINTER(CrnInfo), _vp],
     "krcn_sscn_step": [_vp, _i, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _d, _d, _i, _i, _vp, _vp,
                        ctypes.POINTER(CrnInfo), _vp],
+    "krcn_cubic_cg": [_vp, _vp, _vp, _d, _d, _d, _d, _i, _d, _i, _vp, ctypes.POINTER(CubicCgInfo), _vp],
     "krcn_gradient_block": [_vp, _i, _vp, _vp, _i, _vp, _dp, _vp, _vp],
     "krcn_value_block": [_vp, _i, _vp, _vp, _i, _vp, _dp, _dp, _vp],
     "krcn_cubic_tridiag_block": [_vp, _i, _i, _ip, _dp, _dp, _dp, _dp, _dp, _d, _i, _dp, ctypes.POINTER(CrnInfo), _vp],

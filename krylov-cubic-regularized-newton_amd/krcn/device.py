@@ -632,6 +632,27 @@ class DeviceCSR:
              _ptr(x_new), _ptr(Ax_new), ctypes.byref(info), _stream(self.device))
         return x_new, Ax_new, info
 
+    # -- the full-space cubic subproblem on the device --------------------------
+    def cubic_cg(self, w, g, M, l2=0.0, r0=0.1, eps=1e-8, it_max=100, cg_rtol=None, cg_maxiter=None, out=None):
+        """argmin_s <g,s> + 1/2 s^T H s + M/3 ||s||^3 for H = X^T diag(w) X / n
+        + l2 I behind one library call (krcn_cubic_cg): scipy's scalar Newton
+        on phi(lam) from r0 with every (H + lam I)^{-1} applied by `cg_solve`'s
+        conjugate gradients (rtol cg_rtol, default eps; at most cg_maxiter
+        updates per solve, default 10 d), the decisions taken on the device.
+        Returns (s, info): s a device d-vector (zeros when the solve failed),
+        info a _lib.CubicCgInfo (solver_it, solver_status — 0 ok, 1 not
+        positive definite, 2 derivative zero, 3 it_max reached with the last
+        iterate returned, 4 non-finite —, cg_solves, cg_unconverged,
+        cg_iterations, ticks, reg_coef, lam, model_decrease, s_norm)."""
+        self._check(w, self.n, "w")
+        self._check(g, self.d, "g")
+        out = self.empty_d() if out is None else self._check(out, self.d, "out")
+        info = _lib.CubicCgInfo()
+        call("krcn_cubic_cg", self._h, _ptr(w), _ptr(g), float(l2), float(M), float(r0), float(eps), int(it_max),
+             float(eps if cg_rtol is None else cg_rtol), 0 if cg_maxiter is None else int(cg_maxiter), _ptr(out),
+             ctypes.byref(info), _stream(self.device))
+        return out, info
+
     # -- the batched Krylov-CRN step: k problems over one X --------------------
     @staticmethod
     def _per_column(v, k, name):

@@ -13,7 +13,8 @@ device kernel, with the backtracking trials enqueued in guarded batches.
 
 The comparison methods of cubic_newton.py run on the same device kernels:
 Cubic_LS (full-space CRN: "CG" solves with device conjugate gradients on the
-HVP, krcn_cg_solve; "full" factors the dense Hessian built from HVPs) and SSCN
+HVP, krcn_cg_solve — or, with device_solver=True, the whole subproblem behind
+one krcn_cubic_cg call; "full" factors the dense Hessian built from HVPs) and SSCN
 (coordinate subspaces: partial gradient / Hessian and the incremental Ax
 update on the device).  Lanczos also accepts any callable operator.
 
@@ -470,11 +471,26 @@ class Cubic_LS(Optimizer):
     the reference's `cg(..., tol=epsilon)`, cubic.py:152-182).
     cubic_solver="full": the dense Hessian (loss.hessian, built from HVPs on the
     device) goes to the host subproblem solver, cubic.py:184-188.
-    Arguments and trace as the reference."""
+    Arguments and trace as the reference.
+
+    device_solver=True (not in the reference; off by default, "CG" only,
+    unsharded losses) solves the subproblem behind one krcn_cubic_cg call
+    instead of a host root_scalar loop over krcn_cg_solve: the Newton iteration
+    on lam and every CG solve's control stay on the device.  The line search
+    stays on the host.  A failed solve raises: LinAlgError (H + lam I not
+    positive definite), ArithmeticError (phi' = 0), FloatingPointError (a
+    non-finite lam, rho or p.q)."""
 
     def __init__(self, reg_coef=None, cubic_solver="CG", solver_it_max=100, solver_eps=1e-8,
-                 beta=0.5, *args, **kwargs):
+                 beta=0.5, *args, device_solver=False, **kwargs):
         super().__init__(*args, **kwargs)
+        if device_solver:
+            if cubic_solver != "CG":
+                raise ValueError('device_solver=True runs the "CG" subproblem solver on the device; '
+                                 f"got cubic_solver={cubic_solver!r}")
+            if getattr(self.loss, "shard", None) is not None:
+                raise NotImplementedError("device_solver=True is implemented for unsharded problems")
+        self.device_solver = bool(device_solver)
         self.solver_it = 0
         self.solver_it_max = solver_it_max
         self.solver_eps = solver_eps
@@ -508,6 +524,8 @@ class Cubic_LS(Optimizer):
         # reach: asked for 1e-8 in fp32, every solve would run its 10 d
         # iterations without ever stopping (fp64 keeps the reference's tol)
         rtol = max(float(epsilon), 10.0 * float(torch.finfo(X.dtype).eps))
+        if self.device_solver:
+            return self._cubic_solver_on_device(M, it_max, epsilon, r0, w, rtol)
 
         def cg(lam, rhs):
             x, info = X.cg_solve(w, rhs, shift=l2 + lam, rtol=rtol)
@@ -541,6 +559,25 @@ class Cubic_LS(Optimizer):
         model_decrease = r / 2 * norm_s ** 2 - M / 3 * norm_s ** 3 + X.dot(g, y) / 2
         s = VecContext.for_device(X.device).axpy(-1.0, y, torch.zeros_like(y))
         return s, sol.iterations, r, model_decrease
+
+    def _cubic_solver_on_device(self, M, it_max, epsilon, r0, w, rtol):
+        """cubic_solver_root_CG behind one krcn_cubic_cg call; same return values."""
+        X = self.loss.device_matrix
+        s, info = X.cubic_cg(w, self.grad, M, l2=float(self.loss.l2), r0=r0, eps=epsilon, it_max=it_max,
+                             cg_rtol=rtol)
+        self.cg_iterations += info.cg_iterations
+        if info.cg_unconverged:
+            if self.cg_unconverged == 0:
+                warnings.warn(f"device CG stopped at maxiter in {info.cg_unconverged} of {info.cg_solves} solves "
+                              f"(rtol {rtol:.1e}); counted in cg_unconverged")
+            self.cg_unconverged += info.cg_unconverged
+        if info.solver_status == 1:
+            raise la.LinAlgError("H + lam I is not positive definite (conjugate gradients met p.q <= 0)")
+        if info.solver_status == 2:
+            raise ArithmeticError("cubic subproblem: the derivative of phi was zero")
+        if info.solver_status == 4:
+            raise FloatingPointError("cubic subproblem: a non-finite lam, rho or p.q ended the solve")
+        return s, info.solver_it, info.lam, info.model_decrease
 
     def cubic_solver_root_full(self, M, it_max=100, epsilon=1e-8, r0=0.1):
         """The host subproblem over the dense Hessian (cubic.py:184-188)."""
