@@ -192,6 +192,47 @@ def cubic_solver_root(g, H, M, it_max=100, epsilon=1e-8, r0=0.1):
     return s, sol.iterations, r, dec
 
 
+def cg(op, b, rtol, maxiter, dtype=np.float64):
+    """scipy.sparse.linalg.cg's unpreconditioned loop from x0 = 0 on op(x) = b, as
+    csrc/krcn_cg.hpp states it: rho_0 = b.b, atol = rtol ||b||, ||b|| = 0 returns
+    x = 0 with 0 iterations; iteration k is q = op(p), alpha = rho_k / p.q,
+    x += alpha p, r -= alpha q, rho_{k+1} = r.r, stop when sqrt(rho_{k+1}) < atol,
+    else beta = rho_{k+1} / rho_k and p = p beta + r.  At most `maxiter` updates.
+    dtype=np.float32 keeps x, r, p, q, alpha and beta in float32 and forms the
+    sums in float64 from the float32 entries, as the device does on an fp32
+    handle (`op` is then called with, and its result rounded to, float32).
+    Returns (x, iterations, converged, rnorms): rnorms[k] = ||r_k|| for
+    k = 0..iterations.  Pinned against scipy by tests/test_oracle_cg.py."""
+    dt = np.dtype(dtype)
+    b = np.asarray(b, dtype=dt)
+
+    def dot(u, v):
+        return np.dot(u, v) if dt == np.float64 else np.dot(u.astype(np.float64), v.astype(np.float64))
+
+    x = np.zeros_like(b)
+    rho = dot(b, b)
+    rnorms = [float(np.sqrt(rho))]
+    if rho == 0.0:
+        return x, 0, True, rnorms
+    atol = rtol * np.sqrt(rho)
+    r = b.copy()
+    p = b.copy()
+    for k in range(maxiter):
+        q = np.asarray(op(p), dtype=dt)
+        alpha = dt.type(rho / dot(p, q))
+        x += alpha * p
+        r -= alpha * q
+        rho_new = dot(r, r)
+        rnorms.append(float(np.sqrt(rho_new)))
+        if np.sqrt(rho_new) < atol:
+            return x, k + 1, True, rnorms
+        beta = dt.type(rho_new / rho)
+        p *= beta
+        p += r
+        rho = rho_new
+    return x, maxiter, False, rnorms
+
+
 def krylov_crn(A, b, x0, m=10, reg_coef=1e-3, it_max=10, beta=0.5, solver_eps=1e-8, l2=0.0,
                lanczos_fn=lanczos):
     """`it_max` steps of Cubic_Krylov_LS.step (cubic.py:265-309) from x0.
