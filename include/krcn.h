@@ -509,6 +509,31 @@ krcn_status krcn_lanczos(krcn_csr* h, const void* w, const void* g, int m,
                          double* alphas_host, double* betas_host,
                          krcn_lanczos_info* info_host, void* stream);
 
+/* SYNCHRONOUS.  The reorthogonalisation of krcn_lanczos (reorth = 1) on a
+ * caller's basis, outside any recurrence: classical Gram-Schmidt twice,
+ *   z1 = z - V_k^T (V_k z),  z2 = z1 - V_k^T (V_k z1),  z <- z2 in place,
+ * over the first k rows V_k of the row-major device array V (rows of d = the
+ * handle's column count, contiguous).  V need NOT be orthonormal: the call
+ * applies the two sweeps as written, whatever V holds, and leaves V untouched.
+ * The same launches as a recurrence step that sweeps k rows run: the 1 KiB-row-
+ * piece sweeps when V and z are 16-byte aligned and rows are whole 16-byte
+ * vectors (d * sizeof(T) % 16 == 0), else the batched sweeps; *path_host
+ * receives 1 for the former and 0 for the latter.  *norm2_host receives
+ * ||z2||^2 as the recurrence forms the next beta^2: the sweeps' per-block
+ * partials (of the rounded, stored z2) added in the recurrence's fixed order.
+ * Either out pointer may be NULL.  Products and sums are in double for both
+ * dtypes, in a fixed order: bitwise equal from call to call.
+ * Workspace: as an unsharded krcn_lanczos(reorth = 1) with m = k + 1 reserves
+ * it on its first call (krcn_csr_reserve(h, k + 1, 1) beforehand makes the
+ * call allocation-free); builds no pass plans.  The device Lanczos state of
+ * the handle is reset, as by a recurrence's start.
+ * KRCN_ERR_INVALID before any HIP call: k outside 1..2043, a null handle, a
+ * null V or z.  Sharded handles: KRCN_ERR_UNSUPPORTED.
+ * What optimizer/cubic.py's Lanczos over a callable A needs for reorth=True
+ * (build-only extension; not in the reference). */
+krcn_status krcn_cgs2(krcn_csr* h, int k, const void* V, void* z,
+                      double* norm2_host, int* path_host, void* stream);
+
 /* ---- batched Lanczos: k recurrences in lockstep over the block HVP --------- */
 /* SYNCHRONOUS on return of alphas/betas/info.  k independent recurrences of
  * krcn_lanczos (reorth = 0) over one X, advanced together: every step runs one

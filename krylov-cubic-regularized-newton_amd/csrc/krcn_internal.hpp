@@ -511,6 +511,11 @@ krcn_status lanczos_f64(krcn_csr* h, const double* w, const double* g, int m, in
 krcn_status lanczos_f32(krcn_csr* h, const float* w, const float* g, int m, int reorth, double tol, double l2,
                         float* V, double* alphas_host, double* betas_host, krcn_lanczos_info* info, hipStream_t s,
                         bool enqueue_only = false);
+// krcn_cgs2 per dtype (arguments already checked): reorth_cgs2 on the caller's V and z, synchronous.
+krcn_status cgs2_f64(krcn_csr* h, int k, const double* V, double* z, double* norm2_host, int* path_host,
+                     hipStream_t s);
+krcn_status cgs2_f32(krcn_csr* h, int k, const float* V, float* z, double* norm2_host, int* path_host,
+                     hipStream_t s);
 
 // The results of a recurrence from the mapped block k_lz_final packed (state,
 // alphas[0..m), betas[0..m-1)), after the stream has passed it: the

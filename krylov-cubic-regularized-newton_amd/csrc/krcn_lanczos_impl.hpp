@@ -637,3 +637,29 @@ static krcn_status lanczos_impl(krcn_csr* h, const T* w, const T* g, int m, int 
   lanczos_results(h, m, alphas_host, betas_host, info);
   return KRCN_OK;
 }
+
+// krcn_cgs2: reorth_cgs2 on a caller's z and the first k rows of a caller's V,
+// outside any recurrence.  The workspace is an unsharded krcn_lanczos's for
+// m = k + 1 (the step that sweeps k rows); the state flag, which a recurrence
+// that broke down leaves set and every sweep obeys, is cleared as an m = 1
+// recurrence clears it (k_lz_final_check; no norm partials: gnorm = 0).  The
+// ||z2||^2 partials are summed as the next step's prologue sums them
+// (sum_partials, by k_finish).
+template <typename T>
+static krcn_status cgs2_impl(krcn_csr* h, int k, const T* V, T* z, double* norm2_host, int* path_host,
+                             hipStream_t s) {
+  CHK(reserve_reorth(h, k + 1));
+  const LzCtl<T> c{const_cast<T*>(V), z, h->d, 1, 0, 1, h->st, h->betas_dev, h->pb, 0, 0.0};
+  hipLaunchKernelGGL((k_lz_final_check<T>), dim3(1), dim3(kNT), 0, s, c);
+  LAUNCHCHK();
+  const bool vec = cgs_vec_ok<T>(h, V, z, false, k);
+  int P = 0;
+  CHK(reorth_cgs2<T>(h, V, k, z, false, &P, s));
+  hipLaunchKernelGGL((k_finish<0>), dim3(1), dim3(kNT), 0, s, static_cast<const double*>(h->pb), P, h->scal + 5);
+  LAUNCHCHK();
+  HIPCHK(hipMemcpyAsync(h->hostbuf, h->scal + 5, sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (norm2_host) *norm2_host = h->hostbuf[0];
+  if (path_host) *path_host = vec ? 1 : 0;
+  return KRCN_OK;
+}

@@ -267,6 +267,23 @@ extern "C" krcn_status krcn_lanczos(krcn_csr* h, const void* w, const void* g, i
                                    l2, static_cast<float*>(V), alphas_host, betas_host, info_host, S(stream));
 }
 
+extern "C" krcn_status krcn_cgs2(krcn_csr* h, int k, const void* V, void* z, double* norm2_host, int* path_host,
+                                 void* stream) {
+  if (k < 1 || k >= kLzMaxM) return fail(KRCN_ERR_INVALID, "krcn_cgs2: k = %d outside [1, %d]", k, kLzMaxM - 1);
+  if (!h) return fail(KRCN_ERR_INVALID, "krcn_cgs2: null handle");
+  if (!V || !z) return fail(KRCN_ERR_INVALID, "krcn_cgs2: null argument");
+  if (h->shard != KRCN_SHARD_NONE) return fail(KRCN_ERR_UNSUPPORTED, "krcn_cgs2: implemented for unsharded handles");
+  CHK(set_device(h));
+  if (h->d == 0) {   // nothing to sweep
+    if (norm2_host) *norm2_host = 0.0;
+    if (path_host) *path_host = 0;
+    return KRCN_OK;
+  }
+  return h->dtype == KRCN_F64
+             ? cgs2_f64(h, k, static_cast<const double*>(V), static_cast<double*>(z), norm2_host, path_host, S(stream))
+             : cgs2_f32(h, k, static_cast<const float*>(V), static_cast<float*>(z), norm2_host, path_host, S(stream));
+}
+
 extern "C" krcn_status krcn_basis_combine(krcn_csr* h, int m_eff, const void* V, const double* s_host,
                                           const void* x, void* x_new, void* stream) {
   if (!h || !V || !s_host || !x || !x_new) return fail(KRCN_ERR_INVALID, "krcn_basis_combine: null argument");

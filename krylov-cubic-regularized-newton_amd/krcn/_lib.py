@@ -119,6 +119,7 @@ SIGNATURES = {
     "krcn_hvp_block": [_vp, _i, _vp, _i, _vp, _vp, _dp, _vp],
     "krcn_lanczos": [_vp, _vp, _vp, _i, _i, _d, _d, _vp, _dp, _dp,
                      ctypes.POINTER(LanczosInfo), _vp],
+    "krcn_cgs2": [_vp, _i, _vp, _vp, _dp, ctypes.POINTER(ctypes.c_int), _vp],
     "krcn_lanczos_block": [_vp, _i, _vp, _i, _vp, _i, _d, _dp, _vp, _dp, _dp,
                            ctypes.POINTER(LanczosInfo), _vp],
     "krcn_basis_combine_block": [_vp, _i, _i, _vp, _dp, _vp, _vp, _vp],

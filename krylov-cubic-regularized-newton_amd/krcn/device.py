@@ -443,6 +443,26 @@ class DeviceCSR:
         me = info.m_eff
         return V, al_b[:me].copy(), be_b[:max(me - 1, 0)].copy(), info
 
+    def cgs2(self, V, z, k=None):
+        """z <- (I - Vk^T Vk)(I - Vk^T Vk) z in place over the first k rows of V
+        (krcn_cgs2: the reorthogonalisation of lanczos(reorth=True) on a
+        caller's basis, which need not be orthonormal).  V is a contiguous
+        (rows >= k, d) tensor and z a contiguous d-vector; either may be a view
+        into a larger buffer.  Returns (norm2, path): ||z2||^2 as the
+        recurrence sums it, and 1 for the 1 KiB-piece sweeps, 0 for the batched."""
+        if (not isinstance(V, torch.Tensor) or V.dtype != self.dtype or V.device != self.device
+                or V.dim() != 2 or V.shape[1] != self.d or not V.is_contiguous()):
+            raise ValueError(f"V must be a contiguous (rows, {self.d}) {self.dtype} tensor on {self.device}")
+        k = V.shape[0] if k is None else int(k)
+        if k < 1 or k > V.shape[0]:
+            raise ValueError(f"k = {k} outside [1, {V.shape[0]}]")
+        self._check(z, self.d, "z")
+        norm2, path = ctypes.c_double(), ctypes.c_int(-1)
+        call("krcn_cgs2", self._h, k, _ptr(V), _ptr(z), ctypes.byref(norm2), ctypes.byref(path),
+             _stream(self.device))
+        self._reorth_m = max(self._reorth_m, k + 1)
+        return float(norm2.value), int(path.value)
+
     # -- batched Lanczos: k recurrences in lockstep over the block HVP --------
     def lanczos_block(self, w, G, m, tol=1e-6, l2=0.0, V=None):
         """k independent Lanczos recurrences over one X, advanced together

@@ -167,6 +167,60 @@ def lanczos_cgs2(op, v, m=10, tol=1e-6):
     return V, alphas, betas, beta
 
 
+def cgs2_apply(V, z, dtype=np.float64):
+    """What krcn_cgs2 computes, from the inputs as given (already rounded to
+    `dtype`): z1 = z - V^T (V z), z2 = z1 - V^T (V z1) over the rows of V
+    (k x d, NOT assumed orthonormal), every product and sum in np.longdouble.
+    dtype float32 rounds z1 and z2 to float32, as the kernels store them (z2 is
+    then formed from the rounded z1).  Returns (z1, z2, ||z2||^2, S1, S2):
+    z1, z2 longdouble arrays, the norm of the returned z2, and the scales
+    S1 = |z| + |V|^T (|V| |z|), S2 = |z1| + |V|^T (|V| |z1|) (float64) that
+    cgs2_bound turns into a component-wise error bound."""
+    L = np.longdouble
+    f32 = np.dtype(dtype) == np.float32
+    Vl = np.asarray(V).astype(L)
+    zl = np.asarray(z).astype(L)
+
+    def stored(a):
+        return a.astype(np.float32).astype(L) if f32 else a
+
+    z1 = stored(zl - Vl.T @ (Vl @ zl))
+    z2 = stored(z1 - Vl.T @ (Vl @ z1))
+    Va = np.abs(np.asarray(V, dtype=np.float64))
+    S1 = np.abs(zl).astype(np.float64)
+    S1 = S1 + Va.T @ (Va @ S1)
+    S2 = np.abs(z1).astype(np.float64)
+    S2 = S2 + Va.T @ (Va @ S2)
+    return z1, z2, L(np.dot(z2, z2)), S1, S2
+
+
+def cgs2_bound(V, z1, z2, S1, S2, dtype=np.float64):
+    """Component-wise bound on |z2_device - z2_ref| for krcn_cgs2 against
+    cgs2_apply, and the bound on its ||z2||^2.  Every device dot and update is a
+    double sum of at most d + k terms in some fixed order, so with u = 2^-53 and
+    gamma = (d + k + 8) u the standard inner-product bound gives pass 1 an
+    error of at most gamma S1 per component, and pass 2
+        gamma (S2 + |V|^T (|V| gamma S1) + gamma S1):
+    its own rounding on the scale S2, plus pass 1's error carried through
+    I - V^T V.  float32 storage adds one float32 ulp of z2 (the final rounding
+    may fall on the other side) and a one-ulp flip of the stored z1 carried
+    through pass 2, u32 (|z1| + |V|^T (|V| |z1|)) = u32 S2, u32 = 2^-23.
+    ||z2||^2: 2 ||z2|| ||bound||_2 + d u ||z2||^2 (the error of z2 through the
+    square, and the double sum of d squares).  Returns (bound, norm2_bound)."""
+    k, d = np.shape(V)
+    u = 2.0 ** -53
+    gamma = (d + k + 8) * u
+    Va = np.abs(np.asarray(V, dtype=np.float64))
+    e1 = gamma * np.asarray(S1, dtype=np.float64)
+    bound = gamma * (np.asarray(S2, dtype=np.float64) + Va.T @ (Va @ e1) + e1)
+    z2a = np.abs(np.asarray(z2)).astype(np.float64)
+    if np.dtype(dtype) == np.float32:
+        u32 = 2.0 ** -23
+        bound = bound + u32 * z2a + u32 * np.asarray(S2, dtype=np.float64)
+    n2 = float(z2a @ z2a)
+    return bound, 2.0 * np.sqrt(n2) * float(np.linalg.norm(bound)) + d * u * n2
+
+
 def cubic_solver_root(g, H, M, it_max=100, epsilon=1e-8, r0=0.1):
     """Newton on lam^2 - M^2 ||s(lam)||^2 for min <g,s> + 1/2 s^T H s + M/3 ||s||^3
     (cubic.py:40-75, dense branch)."""
