@@ -762,6 +762,55 @@ krcn_status krcn_cubic_cg(krcn_csr* h, const void* w, const void* g, double l2, 
                           double eps, int it_max, double cg_rtol, int cg_maxiter /* <= 0: 10 d */,
                           void* s /* d-vector, out */, krcn_cubic_cg_info* info_host, void* stream);
 
+/* ---- the dense Hessian as one Gram product (fp64 MFMA) -------------------- */
+/* Asynchronous.  H (DEVICE, d x d doubles, row-major) = X^T diag(w) X / n_global
+ * + l2 I, computed as A diag(w) A^T over the dense image A of X^T that a
+ * KRCN_PLAN_DENSE pass 2 owns (d rows of ld >= n stored values), with
+ * v_mfma_f64_16x16x4_f64.  w: a DEVICE n-vector of the handle's dtype
+ * (krcn_weights' output).  The arithmetic is fp64 whatever the handle's dtype
+ * and the image's stored width are (stored floats are widened, which is exact):
+ * an fp64 handle under KRCN_VALUES_F32 computes with double(float(X)).
+ * One workgroup computes one 64 x 64 tile (ta, tb), tb >= ta, of the upper
+ * triangle over 32-entry slabs of the summed index r; tiles below one per CU are
+ * split along r (krcn_gram_geometry; krcn_csr_set_gram_split forces the split).
+ * Sum order of an entry: each w_r x_rb is rounded to fp64 once (the reference's
+ * A.T * weights), then the terms x_ra (w_r x_rb) are accumulated by fused
+ * multiply-adds, r ascending inside a split; the split sums are added in split
+ * order by a second kernel; then s / n_global with a true division, plus l2 on
+ * the diagonal, as krcn_hvp's expression.  No atomics: the bits depend on the
+ * shape and the split count alone, and two calls return the same bytes.
+ * Symmetry: H[a][b] and H[b][a] are written from the same sum, so H is exactly
+ * symmetric; every entry of the d x d output is written exactly once, whatever
+ * it held before.  w is never read at or past n.
+ * n == 0 or nnz == 0: H = l2 I without reading the image.  d == 0: KRCN_OK,
+ * nothing launched.  KRCN_ERR_INVALID before any HIP call: a null w, H or
+ * handle.  Sharded handles get KRCN_ERR_UNSUPPORTED, and so does a handle whose
+ * pass-2 plan is not KRCN_PLAN_DENSE (call krcn_csr_set_pass_format(h, 2,
+ * KRCN_FORMAT_DENSE); pass 1 may have any format).  Builds pass plans on first
+ * use, before any plan pointer is read.
+ * Allocation: with a split above 1 the raw tiles of the splits (tiles x split x
+ * 32 KiB) live in one buffer of the handle's owner table, counted by
+ * krcn_csr_owned_bytes, allocated by the first call that needs it and grown
+ * (freed and reallocated) only when a later call needs more; split 1 allocates
+ * nothing.
+ * Replaces hessian, loss.py:249-255. */
+krcn_status krcn_hessian_gram(krcn_csr* h, const void* w, double l2, double* H, void* stream);
+/* Split of krcn_hessian_gram along the summed index: 0 the rule (auto), else
+ * 1..256 workgroups per tile, taken as it is (tests force small shapes across
+ * splits; a split beyond the slab count leaves some workgroups a zero sum).
+ * Builds nothing.  KRCN_ERR_INVALID outside 0..256. */
+krcn_status krcn_csr_set_gram_split(krcn_csr* h, int split);
+/* The cut of krcn_hessian_gram's work for a d-column, n-row matrix under a
+ * split (0: the rule).  Host arithmetic only: needs no device.  out_host (8
+ * entries) = {tile edge T, slab entries KS, tiles per side ceil(d / T),
+ * upper-triangle tiles, slabs ceil(n / KS), split, grid (tiles x split),
+ * workspace bytes of the split partials (0 at split 1)}.  The rule: split 1 when
+ * the tiles number at least one per CU (256), else the smallest split that
+ * reaches that, while every split keeps 8 slabs and the partials stay within
+ * 256 MiB.  KRCN_ERR_INVALID: d outside [0, 2^20], n outside [0, 2^31), split
+ * outside 0..256, a null out_host. */
+krcn_status krcn_gram_geometry(int64_t d, int64_t n, int split, int64_t* out_host);
+
 /* ---- the batched Krylov-CRN step: k problems over one X per call ---------- */
 /* The batch forms of krcn_gradient, the loss value, krcn_cubic_tridiag and
  * krcn_crn_step over the (L, k) blocks of the block products (element (i, c)

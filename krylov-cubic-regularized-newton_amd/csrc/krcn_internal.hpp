@@ -14,6 +14,8 @@
 //   krcn_sscn.hip        the dense cubic subproblem and the one-call SSCN step (krcn_cubic_dense.hpp)
 //   krcn_cubic_cg.hip    the full-space cubic subproblem, Newton over CG in one call (krcn_cgn.hpp; its
 //                        state rule, krcn_cgn_state.hpp, is host-only like the three below)
+//   krcn_gram.hip        the dense Hessian as a Gram product over the dense X^T image, fp64 MFMA (krcn_gram.hpp;
+//                        its cut of the work, krcn_gram_geom.hpp, is host-only like the three below)
 //   krcn_lanczos_f64.hip / krcn_lanczos_f32.hip
 //                        the device Lanczos recurrence (krcn_lanczos_impl.hpp), one dtype each
 // Three host-only headers (plain C++17, no HIP header: they also build with g++
@@ -340,7 +342,10 @@ struct krcn_csr {
   double* cgn_st = nullptr;   //   the chain state, then the two partial arrays of a turn's sums
   double* cgn_res = nullptr;  //   pinned, mapped host record the turn that ends the chain writes
   double* cgn_res_dev = nullptr;
-  double* crn_ws = nullptr;   // krcn_crn_step / krcn_cubic_tridiag: the chain state, then the subproblem's
+  double* gram_ws = nullptr;  // krcn_hessian_gram (krcn_gram.hip): the raw tiles of its K splits (grown on demand)
+  size_t gram_ws_bytes = 0;
+  int gram_split = 0;         // krcn_csr_set_gram_split (0: the rule of krcn_gram_geom.hpp)
+  double* crn_ws = nullptr;  // krcn_crn_step / krcn_cubic_tridiag: the chain state, then the subproblem's
                               // alphas | betas | s (three kLzMaxM-vectors; its solves work in LDS)
   double* crn_res = nullptr;  //   pinned, mapped host record the judge kernel writes (krcn_crn.hip)
   double* crn_res_dev = nullptr;

@@ -140,6 +140,9 @@ SIGNATURES = {
     "krcn_sscn_step": [_vp, _i, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _d, _d, _i, _i, _vp, _vp,
                        ctypes.POINTER(CrnInfo), _vp],
     "krcn_cubic_cg": [_vp, _vp, _vp, _d, _d, _d, _d, _i, _d, _i, _vp, ctypes.POINTER(CubicCgInfo), _vp],
+    "krcn_hessian_gram": [_vp, _vp, _d, _vp, _vp],
+    "krcn_csr_set_gram_split": [_vp, _i],
+    "krcn_gram_geometry": [_i64, _i64, _i, ctypes.POINTER(_i64)],
     "krcn_gradient_block": [_vp, _i, _vp, _vp, _i, _vp, _dp, _vp, _vp],
     "krcn_value_block": [_vp, _i, _vp, _vp, _i, _vp, _dp, _dp, _vp],
     "krcn_cubic_tridiag_block": [_vp, _i, _i, _ip, _dp, _dp, _dp, _dp, _dp, _d, _i, _dp, ctypes.POINTER(CrnInfo), _vp],

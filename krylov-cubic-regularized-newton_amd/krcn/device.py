@@ -673,6 +673,31 @@ class DeviceCSR:
              ctypes.byref(info), _stream(self.device))
         return out, info
 
+    # -- the dense Hessian as one Gram product ---------------------------------
+    def set_gram_split(self, split=0):
+        """Workgroups per output tile of hessian_gram along the summed index
+        (krcn_csr_set_gram_split): 0 the rule of gram_geometry, else 1..256."""
+        call("krcn_csr_set_gram_split", self._h, int(split))
+
+    def hessian_gram(self, w, l2=0.0, out=None):
+        """H = X^T diag(w) X / n + l2 I (loss.py:249-255) as one weighted Gram
+        product over the dense image of X^T, in fp64 on the matrix instruction
+        (krcn_hessian_gram): a device (d, d) float64 tensor, exactly symmetric,
+        the same bytes on every call.  Needs a dense pass 2 (set_format(5) or
+        set_pass_format(2, 5)); the library's KRCN_ERR_UNSUPPORTED is raised
+        otherwise.  w: the device n-vector `weights` returns."""
+        self._check(w, self.n, "w")
+        if out is None:
+            out = torch.empty((self.d, self.d), dtype=torch.float64, device=self.device)
+        elif (not isinstance(out, torch.Tensor) or out.device != self.device or out.dtype != torch.float64
+              or tuple(out.shape) != (self.d, self.d) or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous ({self.d}, {self.d}) float64 tensor on {self.device}")
+        # an empty tensor has no address: n == 0 never reads w, d == 0 never writes H
+        wp = _ptr(w) if self.n else _ptr(self.indptr)
+        Hp = _ptr(out) if self.d else _ptr(self.indptr)
+        call("krcn_hessian_gram", self._h, wp, float(l2), Hp, _stream(self.device))
+        return out
+
     # -- the batched Krylov-CRN step: k problems over one X --------------------
     @staticmethod
     def _per_column(v, k, name):

@@ -479,11 +479,19 @@ class Cubic_LS(Optimizer):
     on lam and every CG solve's control stay on the device.  The line search
     stays on the host.  A failed solve raises: LinAlgError (H + lam I not
     positive definite), ArithmeticError (phi' = 0), FloatingPointError (a
-    non-finite lam, rho or p.q)."""
+    non-finite lam, rho or p.q).
+
+    gram_hessian=True (not in the reference; off by default, "full" only) builds
+    the dense Hessian of every step as one Gram product on the device
+    (loss.hessian(x, gram=True)); the loss needs a dense X^T image."""
 
     def __init__(self, reg_coef=None, cubic_solver="CG", solver_it_max=100, solver_eps=1e-8,
-                 beta=0.5, *args, device_solver=False, **kwargs):
+                 beta=0.5, *args, device_solver=False, gram_hessian=False, **kwargs):
         super().__init__(*args, **kwargs)
+        if gram_hessian and cubic_solver != "full":
+            raise ValueError('gram_hessian=True builds the dense Hessian of the "full" subproblem solver; '
+                             f"got cubic_solver={cubic_solver!r}")
+        self.gram_hessian = bool(gram_hessian)
         if device_solver:
             if cubic_solver != "CG":
                 raise ValueError('device_solver=True runs the "CG" subproblem solver on the device; '
@@ -596,7 +604,7 @@ class Cubic_LS(Optimizer):
             self.value = loss.value(self.x)
         self.grad = loss.gradient(self.x)
         if self.cubic_solver == self.cubic_solver_root_full:
-            self.hess = loss.hessian(self.x)
+            self.hess = loss.hessian(self.x, gram=True) if self.gram_hessian else loss.hessian(self.x)
         if loss.norm(self.grad) < self.tolerance:
             return
         reg_coef = self.reg_coef * self.beta

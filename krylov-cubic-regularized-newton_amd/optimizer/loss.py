@@ -453,15 +453,25 @@ class LogisticRegression(Oracle):
         if self.shard is not None:
             raise NotImplementedError(f"{what} is implemented for unsharded problems")
 
-    def hessian(self, x, block=None):
+    def hessian(self, x, block=None, gram=False):
         """Dense Hessian X^T diag(w) X / n + l2 I (loss.py:249-255): the
         coordinate-block kernel over all columns for d <= KRCN_COORD_MAX, one
         device HVP per column above that; numpy (d, d), for the full-space CRN
         at small d.  block=k (1..KRCN_BLOCK_MAX) builds the d > KRCN_COORD_MAX
         Hessian from block HVPs over k unit vectors at a time instead: d / k
         matrix reads, not d (the sums of a long row then run in the block
-        kernels' order, so entries may differ from block=None in the last bits)."""
+        kernels' order, so entries may differ from block=None in the last bits).
+        gram=True (any d; needs a dense X^T image: format="dense", or
+        device_matrix.set_pass_format(2, KRCN_FORMAT_DENSE)) builds it as one
+        weighted Gram product in fp64 on the matrix instruction
+        (DeviceCSR.hessian_gram): exactly symmetric, entries within rounding of
+        the default's; the library's error is raised when pass 2 is not dense."""
+        if gram and block is not None:
+            raise ValueError("gram=True builds the Hessian in one product: it takes no block")
         self._no_shards("the dense / coordinate Hessian")
+        if gram:
+            H = self.device_matrix.hessian_gram(self._weights_for(x), l2=float(self.l2))
+            return H.cpu().numpy()
         if block is not None and not 1 <= int(block) <= _lib.KRCN_BLOCK_MAX:
             raise ValueError(f"block must be None or 1..{_lib.KRCN_BLOCK_MAX}, got {block!r}")
         if self.dim <= _lib.KRCN_COORD_MAX:
