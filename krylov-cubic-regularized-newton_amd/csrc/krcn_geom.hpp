@@ -129,7 +129,10 @@ constexpr int kWinChunk = 256;               // nonzeros per staging step (4 per
 constexpr int kWinTMax = 6;                  // accumulate mode: tiles per wave (register sums)
 constexpr int kWinPad = kWinChunk + 8;       // array padding: unconditional chunk loads stay in bounds
 constexpr int kWinRing = 3;                  // chunk slots in flight per wave (slices mode)
-constexpr int kWinBatch = 26;                // slices mode: tiles per batch of tile bases and rows (32 - the look-ahead)
+#ifndef KRCN_WIN_CLAIM
+#define KRCN_WIN_CLAIM 1
+#endif
+constexpr int kWinClaimRun = KRCN_WIN_CLAIM; // slices mode: consecutive tiles a wave takes per claim (win_claim_run)
 // LDS: window + 16 slabs of kWinChunk + the reduction scratch must fit 160 KiB
 template <typename T> struct WinGeom {
   static constexpr int kSlabBytes = kWinWaves * kWinChunk * int(sizeof(T));
@@ -155,6 +158,41 @@ KRCN_HD inline void win_block_slice(int b, int G, int S, int kpb, int& slice, in
   const int slot = x * q + (x < r ? x : r) + b / 8;
   slice = slot / kpb;
   chunk = slot % kpb;
+}
+
+// Slices mode: how a block's waves share the tiles [t0, t1) of its segment
+// (win_stream).  The first ring fill is dealt statically — wave w takes tiles
+// t0 + w + kWinWaves k, k < kWinRing, those below t1 — and the rest, the pool
+// [win_claim_start, t1), is handed out by one LDS counter per block that
+// counts the claims drawn: claim c = 0, 1, ... (whichever wave draws it) takes
+// win_claim_run's tiles, `run` consecutive ones.  A wave goes on claiming
+// until a claim reaches t1 (and a few claims further: its look-ahead), so
+// claims past the pool are drawn; they denote no tiles.
+KRCN_HD inline int win_claim_start(int t0, int t1) {
+  const int n = t1 - t0, p = kWinWaves * kWinRing;
+  return t0 + (n < p ? (n > 0 ? n : 0) : p);
+}
+// Tile k < kWinRing of wave w's static deal, or -1 where the segment ends before it.
+KRCN_HD inline int win_static_tile(int t0, int t1, int w, int k) {
+  const int t = t0 + w + kWinWaves * k;
+  return t < t1 ? t : -1;
+}
+struct WinRun {
+  int first, n;   // tiles [first, first + n); n == 0: none (first is then the pool's end)
+};
+KRCN_HD inline WinRun win_claim_run(int t0, int t1, int c, int run = kWinClaimRun) {
+  const int start = win_claim_start(t0, t1);
+  const int pool = t1 > start ? t1 - start : 0;
+  const int before = c <= pool / run ? c * run : pool;   // tiles of the claims before c, clamped (no overflow)
+  const int taken = before < pool ? before : pool;
+  const int left = pool - taken;
+  return WinRun{start + taken, left < run ? left : run};
+}
+// The tile whose bounds a wave reads for tile t: t itself below t1, else the
+// segment's last tile (at least 0), whose bounds are loaded and not used.
+KRCN_HD inline int win_tile_clamp(int t, int t1) {
+  t = t < t1 ? t : t1 - 1;
+  return t > 0 ? t : 0;
 }
 
 // The per-block X^T copies of one-piece window-accum plans (EpiLz1X).

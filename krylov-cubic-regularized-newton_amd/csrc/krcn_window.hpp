@@ -26,8 +26,9 @@
 //    kernel with a lane cap of 64 runs either.
 //  * Segments {slice, t0, t1, flags}: block b runs segs[b * stride + i]
 //    (the first entry carries the count); wave w takes tiles t0 + w,
-//    t0 + w + 16, ...; kSegLoad loads the slice's window first, kSegFlush
-//    hands the row sums to the epilogue.
+//    t0 + w + 16, ... (slices mode: its first three so, then whichever tiles
+//    it claims from the block's counter, win_stream); kSegLoad loads the
+//    slice's window first, kSegFlush hands the row sums to the epilogue.
 //  Two ways to use it:
 //  * accumulate (pass over X^T, few slices): every block owns one tile range
 //    and walks all S slices over it (one segment per slice, flush on the
@@ -319,13 +320,15 @@ struct TileB {
   }
 };
 
-// Tile bases of a wave's tiles tw + 16 k, a batch at a time, in two registers:
+// Tile bases of a wave's statically dealt tiles tw + 16 k in two registers:
 // lane i holds e0 / e1 of tile k = kb + i (clamped into the segment), one
 // vector load each for all of them, read lane-wise (v_readlane) as the ring
 // reaches each tile.  kRows (slices mode): lanes 0-31 hold e0 / e1 of tile
 // kb + i and lanes 32-63 the row bounds r0 / r1 of the same 32 tiles (they
 // follow the slice's bases, `roff` entries on: one base pointer), so the rows
-// cost neither a register nor a load more than the bases.
+// cost neither a register nor a load more than the bases.  Accumulate mode
+// reads all of a wave's tiles from it, slices mode the first kWinRing (the
+// later ones are claimed and load their bounds one tile at a time, win_stream).
 // Loading each tile's bases on its own and broadcasting them (readfirstlane)
 // made every tile wait for its load, and vmcnt retires in issue order: that
 // wait drained the whole ring of chunk loads once per tile (round 5, ISA of
@@ -561,116 +564,170 @@ __device__ __forceinline__ void fold_drain(const EpiSliceFold<T>& e, WinFold& f,
 }
 
 // Tiles of one segment in flush mode (every tile's row sums go to the
-// epilogue when final): a runtime loop over the wave's tiles t0 + wave + 16 k
-// with a ring of kWinRing chunk slots — while tile k is consumed the row
-// bounds / epilogue operands of tile k + 1 and the chunk of tile k + 2 are in
-// flight, and the scalar bounds of tile k + 3 are loading.  The window (if
-// the segment loads one) is stored into LDS after the first chunks are issued.
+// epilogue when final): a ring of kWinRing chunk slots per wave — while a tile
+// is consumed the row bounds / epilogue operands of the wave's next tile and
+// the chunk of the one after are in flight, and the bounds of the third are
+// loading.  The window (if the segment loads one) is stored into LDS before
+// the first chunks are issued.
+// Which tiles a wave runs (krcn_geom.hpp win_claim_*): its first kWinRing
+// tiles are dealt statically (t0 + wave + 16 k, bounds from the WinTiles the
+// kernel loaded beside the window fetch, chunk loads straight behind the
+// window store), every later one it claims from the block's LDS counter as a
+// ring slot comes free, so a wave that runs slowly (memory latency, LDS
+// conflicts, the SIMD's other waves) takes fewer tiles and the block's waves
+// end within about a tile of each other.  The partials are per (slice, row)
+// and the combine's order is fixed: no bit depends on who ran a tile.
+// Per tile finished the wave
+//  * reads the claim it issued one tile ago (one ds_add_rtn a wave: returned
+//    long since behind the tile's LDS traffic) and issues the next,
+//  * loads the claimed tile's four bounds (tb[t], tb[t + 1] and the two row
+//    starts `roff` entries on: lanes 0-3 of one dword load) BEFORE the row-end
+//    and chunk loads of the tiles ahead — vmcnt retires in issue order, so the
+//    wait for the bounds a tile later (v_readlane) leaves those in flight
+//    (the trap recorded at WinTiles),
+//  * and takes the bounds into the freed slot's SGPRs once the tile is done.
+// A claim at or past t1 gives a tile that is not `ok`: clamped bounds with no
+// elements (loads in bounds, nothing summed, nothing stored), and the wave
+// leaves the loop at the first such tile it reaches.
 template <typename T, typename TS, int R, class Epi>
 __device__ __forceinline__ void win_stream(int segno, const WinSeg& sg, const WinArgs& a,
                                            const T (&tmp)[WinGeom<T>::kPer], bool store_win, int rot, T* win,
                                            T* slab, const Epi& epi, int wave, int lane,
-                                           typename RedOf<Epi>::type& red, WinTiles tl) {
+                                           typename RedOf<Epi>::type& red, const WinTiles& tl, int* claim) {
+  static_assert(!IsFoldEpi<Epi>::value,
+                "KRCN_FOLD indexes a wave's tiles statically: not ported to the claimed tiles of win_stream");
+  static_assert(kWinClaimRun >= 1 && kWinRing == 3, "the ring below is written out for three slots");
   const int rows = a.rows;
   const int* tb = win_tb<false>(a, sg.slice);
+  const int roff = a.ntiles + 1;
   const unsigned short* ro = a.ro + int64_t(sg.slice) * rows;
   const unsigned short* widx = a.widx;
   const TS* wval = static_cast<const TS*>(a.wval);
-  const int tw = sg.t0 + wave;
-  const int nt = sg.t1 - tw > 0 ? (sg.t1 - tw + kWinWaves - 1) / kWinWaves : 0;
-  // tiles in batches of kWinBatch: the ring's look-ahead (5 tiles) stays
-  // inside one 32-tile batch of tile bases and rows; a new batch (past 26
-  // tiles of a wave: more than 416 tiles a block) restarts the ring behind
-  // its load
-  const int nb = (nt + kWinBatch - 1) / kWinBatch;
-  WinFold fold;   // (the slice-combine fold only: IsFoldEpi)
-  if (nb == 0 && store_win) {   // a wave without tiles still takes part in the window store
-    lds_block_barrier();
-    win_store<T>(tmp, win, sg.slice, a, rot);
-    lds_block_barrier();
-  }
-  for (int bi = 0; bi < nb; ++bi) {
-    const int kb = bi * kWinBatch;
-    const int kn = nt - kb < kWinBatch ? nt - kb : kWinBatch;
-    if (bi > 0) tl.load<true>(tb, a.ntiles + 1, tw, sg.t1, kb, lane);
-    // tile kb + k, k < 32, from the batch (no memory access): its elements when its chunk is loaded, its rows
-    // only when its row ends are (two tiles later), so few tiles' bounds are live at a time
-    auto bounds = [&](TileB<R>& b, int k) {
-      b.e0 = __builtin_amdgcn_readlane(tl.lo, k);
-      b.e1 = __builtin_amdgcn_readlane(tl.hi, k);
-    };
-    TileB<R> B0, B1, B2;
-    bounds(B0, 0);
-    bounds(B1, 1);
-    bounds(B2, 2);
-    WinChunk<T, TS> c0, c1, c2;
-    RowRaw q0, q1, q2;
-    typename Epi::Pre p0, p1, p2;
-    auto rows_of = [&](TileB<R>& b, int k, RowRaw& q, typename Epi::Pre& pr) {
-      b.set_rows(__builtin_amdgcn_readlane(tl.lo, k + 32), __builtin_amdgcn_readlane(tl.hi, k + 32), b.e0, b.e1);
-      q = tile_row_load<R>(b, ro, lane);
-      const int r = b.r0 + lane;
-      pr = epi.pre(r < rows ? r : rows - 1);
-    };
-    const bool sw = bi == 0 && store_win;
-    // vmcnt retires in issue order: a tile's row ends go out BEFORE the
-    // chunks that must stay in flight while it is consumed
-#if KRCN_WIN_FIRST
-    // the window's loads go out alone: chunk loads issued beside them would
-    // share the CU's memory queue with it while every CU starts up at once
-    if (sw) {
-      lds_block_barrier();   // every wave is done with the previous window
-      win_store<T>(tmp, win, sg.slice, a, rot);
-    }
-    rows_of(B0, 0, q0, p0);
-    win_load(c0, B0.e0, B0.e1, widx, wval, lane);
-    win_load(c1, B1.e0, B1.e1, widx, wval, lane);
-    if (sw) lds_block_barrier();
-#else
-    rows_of(B0, 0, q0, p0);
-    win_load(c0, B0.e0, B0.e1, widx, wval, lane);
-    win_load(c1, B1.e0, B1.e1, widx, wval, lane);
-    if (sw) {
-      lds_block_barrier();   // every wave is done with the previous window
+  if (win_static_tile(sg.t0, sg.t1, wave, 0) < 0) {   // fewer tiles than waves (and no pool): no tile for this wave,
+    if (store_win) {                                  // which still takes part in the window store
+      lds_block_barrier();
       win_store<T>(tmp, win, sg.slice, a, rot);
       lds_block_barrier();
     }
-#endif
-    if (segno < 4 && bi == 0) KRCN_WIN_STAMP(2 + 2 * segno);
-    auto finish = [&](const WinChunk<T, TS>& c, const TileB<R>& b, const RowRaw& q, const typename Epi::Pre& pr,
-                      int k) {
-      int bg, en;
-      tile_row_bounds<R>(b, q, lane, bg, en);
-      const bool coop = KRCN_WIN_COOP && a.S > 1;
-      T open = T(0);   // (coop: the partial sums of a long row that goes on in the tile's next chunk)
-      T s = win_consume(c, bg, en, win, slab, lane, T(0), coop, open);
-      for (int cc = c.hi; cc < b.e1;) {          // tiles longer than one chunk
-        WinChunk<T, TS> cx;
-        win_load(cx, cc, b.e1, widx, wval, lane);
-        s = win_consume(cx, bg, en, win, slab, lane, s, coop, open);
-        cc = cx.hi;
-      }
-      if (k < kn && lane < b.nr) red += epi.row(b.r0 + lane, s, sg.slice, pr);
-      if constexpr (IsFoldEpi<Epi>::value)
-        if (k < kn) fold_after<T, R>(epi, fold, b.r0 / R, rows, lane);
-    };
-    // B0 / B1 / B2: tiles k, k + 1, k + 2, then (as each is finished) k + 3, k + 4, k + 5
-    for (int k = 0; k < kn; k += 3) {
-      rows_of(B1, k + 1, q1, p1);
-      win_load(c2, B2.e0, B2.e1, widx, wval, lane);
-      finish(c0, B0, q0, p0, k);
-      bounds(B0, k + 3);
-      rows_of(B2, k + 2, q2, p2);
-      win_load(c0, B0.e0, B0.e1, widx, wval, lane);
-      finish(c1, B1, q1, p1, k + 1);
-      bounds(B1, k + 4);
-      rows_of(B0, k + 3, q0, p0);
-      win_load(c1, B1.e0, B1.e1, widx, wval, lane);
-      finish(c2, B2, q2, p2, k + 2);
-      bounds(B2, k + 5);
-    }
+    return;
   }
-  if constexpr (IsFoldEpi<Epi>::value) fold_drain<T, R>(epi, fold, rows, lane);
+  struct Tile {
+    TileB<R> b;
+    bool ok;
+  };
+  // static tile k < kWinRing, from the batch (no memory access)
+  auto from_prefix = [&](Tile& x, int k) {
+    x.ok = win_static_tile(sg.t0, sg.t1, wave, k) >= 0;
+    const int e0 = __builtin_amdgcn_readlane(tl.lo, k);
+    const int e1 = __builtin_amdgcn_readlane(tl.hi, k);
+    x.b.set_rows(__builtin_amdgcn_readlane(tl.lo, k + 32), __builtin_amdgcn_readlane(tl.hi, k + 32), e0, x.ok ? e1 : e0);
+  };
+  Tile X0, X1, X2;
+  from_prefix(X0, 0);
+  from_prefix(X1, 1);
+  from_prefix(X2, 2);
+  int clv = 0;      // the claim in flight (lane 0: the claims drawn before it)
+  int cbv = 0;      // the bounds in flight (lanes 0-3) of the tile that takes the next free slot
+  bool okn = false;
+  WinRun rn{0, 0};  // the run claimed last and the tiles taken from it
+  int sub = kWinClaimRun;
+  // One ds_add_rtn per claim, executed by the whole wave without a branch:
+  // lane 0 adds 1 to the block's counter, every other lane adds 0 to a word
+  // of the wave's own slab (an integer add of 0 leaves its bits; distinct
+  // banks, so the instruction costs what a slab write does).  Under
+  // `if (lane == 0)` the compiler reads the result inside that branch, and the
+  // wave waits for the LDS round trip at the issue instead of a tile later.
+  int* const claim_at = lane == 0 ? claim : reinterpret_cast<int*>(slab) + lane;
+  auto claim_issue = [&]() {
+    clv = __hip_atomic_fetch_add(claim_at, lane == 0 ? 1 : 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  };
+  auto fetch_next = [&]() {
+    if (kWinClaimRun == 1 || sub == kWinClaimRun) {
+      rn = win_claim_run(sg.t0, sg.t1, __builtin_amdgcn_readfirstlane(clv));
+      claim_issue();
+      sub = 0;
+    }
+    okn = sub < rn.n;
+    const int t = win_tile_clamp(rn.first + sub, sg.t1);
+    ++sub;
+    cbv = tb[t + (lane & 1) + ((lane & 2) ? roff : 0)];
+  };
+  auto take = [&](Tile& x) {
+    x.ok = okn;
+    const int e0 = __builtin_amdgcn_readlane(cbv, 0);
+    const int e1 = __builtin_amdgcn_readlane(cbv, 1);
+    x.b.set_rows(__builtin_amdgcn_readlane(cbv, 2), __builtin_amdgcn_readlane(cbv, 3), e0, okn ? e1 : e0);
+  };
+  WinChunk<T, TS> c0, c1, c2;
+  RowRaw q0, q1, q2;
+  typename Epi::Pre p0, p1, p2;
+  auto rows_of = [&](const Tile& x, RowRaw& q, typename Epi::Pre& pr) {
+    q = tile_row_load<R>(x.b, ro, lane);
+    const int r = x.b.r0 + lane;
+    pr = epi.pre(r < rows ? r : rows - 1);
+  };
+  // vmcnt retires in issue order: a tile's row ends go out BEFORE the
+  // chunks that must stay in flight while it is consumed
+#if KRCN_WIN_FIRST
+  // the window's loads go out alone: chunk loads issued beside them would
+  // share the CU's memory queue with it while every CU starts up at once
+  if (store_win) {
+    lds_block_barrier();   // every wave is done with the previous window; the claim counter is set
+    win_store<T>(tmp, win, sg.slice, a, rot);
+  }
+  rows_of(X0, q0, p0);
+  win_load(c0, X0.b.e0, X0.b.e1, widx, wval, lane);
+  win_load(c1, X1.b.e0, X1.b.e1, widx, wval, lane);
+  claim_issue();
+  if (store_win) lds_block_barrier();
+#else
+  rows_of(X0, q0, p0);
+  win_load(c0, X0.b.e0, X0.b.e1, widx, wval, lane);
+  win_load(c1, X1.b.e0, X1.b.e1, widx, wval, lane);
+  if (store_win) {
+    lds_block_barrier();   // every wave is done with the previous window; the claim counter is set
+    win_store<T>(tmp, win, sg.slice, a, rot);
+    lds_block_barrier();
+  }
+  claim_issue();
+#endif
+  if (segno < 4) KRCN_WIN_STAMP(2 + 2 * segno);
+  auto finish = [&](const WinChunk<T, TS>& c, const Tile& x, const RowRaw& q, const typename Epi::Pre& pr) {
+    const TileB<R>& b = x.b;
+    int bg, en;
+    tile_row_bounds<R>(b, q, lane, bg, en);
+    const bool coop = KRCN_WIN_COOP && a.S > 1;
+    T open = T(0);   // (coop: the partial sums of a long row that goes on in the tile's next chunk)
+    T s = win_consume(c, bg, en, win, slab, lane, T(0), coop, open);
+    for (int cc = c.hi; cc < b.e1;) {          // tiles longer than one chunk
+      WinChunk<T, TS> cx;
+      win_load(cx, cc, b.e1, widx, wval, lane);
+      s = win_consume(cx, bg, en, win, slab, lane, s, coop, open);
+      cc = cx.hi;
+    }
+    if (x.ok && lane < b.nr) red += epi.row(b.r0 + lane, s, sg.slice, pr);
+  };
+  // X0 / X1 / X2: the wave's current tile and the two after it; a finished slot takes the tile claimed for it
+  for (;;) {
+    fetch_next();
+    rows_of(X1, q1, p1);
+    win_load(c2, X2.b.e0, X2.b.e1, widx, wval, lane);
+    finish(c0, X0, q0, p0);
+    take(X0);
+    if (!X1.ok) break;
+    fetch_next();
+    rows_of(X2, q2, p2);
+    win_load(c0, X0.b.e0, X0.b.e1, widx, wval, lane);
+    finish(c1, X1, q1, p1);
+    take(X1);
+    if (!X2.ok) break;
+    fetch_next();
+    rows_of(X0, q0, p0);
+    win_load(c1, X1.b.e0, X1.b.e1, widx, wval, lane);
+    finish(c2, X2, q2, p2);
+    take(X2);
+    if (!X0.ok) break;
+  }
 }
 
 // Tiles of one segment in accumulate mode: at most kWinTMax tiles per wave,
@@ -842,6 +899,7 @@ __global__ __launch_bounds__(kWinNT, 1) void k_window_pass(WinArgs a, Src src, E
   __shared__ T win[WinGeom<T>::kW];
   __shared__ T slab_all[kWinWaves][kWinChunk];
   __shared__ int fold_n;   // (the slice-combine fold: tiles won by the block)
+  __shared__ int claim;    // slices mode: the claims the block's waves have drawn in the segment (win_stream)
   if constexpr (IsFoldEpi<Epi>::value) {
     if (threadIdx.x == 0) fold_n = 0;   // (ordered before every use by the window barriers)
     epi.nwon = &fold_n;
@@ -850,6 +908,8 @@ __global__ __launch_bounds__(kWinNT, 1) void k_window_pass(WinArgs a, Src src, E
   const WinSeg* bsegs = a.segs + int64_t(blockIdx.x) * a.stride;
   WinSeg sg = bsegs[0];
   const int nseg = sg.flags >> 8;
+  if constexpr (!kAccum)
+    if (threadIdx.x == 0) claim = 0;   // (ordered before every claim by the window barriers)
   const int rot = int((blockIdx.x >> 3) % kPer);
   // Slices mode: block b = slice + S c, so the window fetch goes out without
   // waiting for the segment (the tile bases follow it); accumulate mode: the
@@ -978,6 +1038,11 @@ __global__ __launch_bounds__(kWinNT, 1) void k_window_pass(WinArgs a, Src src, E
         win_fetch<T>(tmp, x, sg.slice, a, rot);
         store_win = true;
       }
+      if constexpr (!kAccum) {   // (no slices layout has a second segment: every block owns one row chunk of one slice)
+        lds_block_barrier();     // every wave has drawn its last claim of the segment before
+        if (threadIdx.x == 0) claim = 0;
+        if (!store_win) lds_block_barrier();   // (else the window barriers order it)
+      }
     }
     if constexpr (kAccum) {
       if (sg.flags & kSegFlush)
@@ -985,7 +1050,7 @@ __global__ __launch_bounds__(kWinNT, 1) void k_window_pass(WinArgs a, Src src, E
       else
         win_accum<T, TS, R, Epi, false>(si, sg, a, tmp, store_win, rot, win, slab, epi, wave, lane, acc, red, tl);
     } else {
-      win_stream<T, TS, R, Epi>(si, sg, a, tmp, store_win, rot, win, slab, epi, wave, lane, red, tl);
+      win_stream<T, TS, R, Epi>(si, sg, a, tmp, store_win, rot, win, slab, epi, wave, lane, red, tl, &claim);
     }
     if (si < 4) KRCN_WIN_STAMP(3 + 2 * si);
   }
