@@ -716,6 +716,91 @@ krcn_status krcn_sscn_step(krcn_csr* h, int k, const int32_t* cols_host, const v
                            double r0, double solver_eps, int solver_it_max, int max_trials, void* x_new,
                            void* Ax_new, krcn_crn_info* info_host, void* stream);
 
+/* ---- the SSCN step over one tridiagonal reduction (k up to 1024) ---------- */
+/* Largest coordinate block of krcn_dense_tridiag, krcn_cubic_dense_tridiag and
+ * krcn_sscn_step_tridiag (= KRCN_COORD_MAX; the reference's experiment script
+ * runs SSCN with subspace dimensions up to 1000). */
+enum { KRCN_SSCN_TRIDIAG_MAX = 1024 };
+
+/* The route.  H is the same for every lam of a solve and every trial of a step,
+ * so it is reduced once, by Householder reflectors, to T = Q^T H Q tridiagonal
+ * with Q's first column along g; the subproblem is then krcn_cubic_tridiag's
+ * (g = b_0 e1, O(k) per lam) and s = Q s_T, with ||s|| = ||s_T|| and
+ * g.s = b_0 (s_T)_0, so the reference's closing expressions are unchanged.
+ * The reduction works in fp64, whatever the handle's dtype, on the bordered
+ * matrix B = [[0, g^T], [g, H]] of order K = k + 1 in full storage: its first
+ * reflector maps g to b_0 e1 (b_0 = -sign(g_0) ||g||, sign(0) = +) and the later
+ * ones leave that direction fixed.  LAPACK dlarfg's conventions without its
+ * rescaling of tiny columns; tau = 0 (the identity, no division) when the column
+ * below the subdiagonal is already zero, so g = 0, a diagonal H and a decoupled
+ * block pass through.  One launch per column j = 0 .. K - 3 with one workgroup
+ * per 4 rows of the trailing block, a fill kernel before and a one-workgroup
+ * closing kernel after; no workgroup waits on another, no atomics, every sum in
+ * a fixed order: the bits depend on k and the data alone.
+ * Workspace: B, the reflector rows, two p vectors, tau / alphas / betas, g, s_T
+ * and the selection: 8 ld (2 (k + 1) + 9) bytes with ld = k + 1 rounded up to a
+ * multiple of 8 (16,999,104 bytes at k = 1024), one buffer of the handle's owner
+ * table, counted by krcn_csr_owned_bytes, allocated by the first call that needs
+ * it and grown (freed and reallocated) only when a later call has a larger k. */
+
+/* Host arithmetic only: needs no device.  The column launches of a reduction of
+ * a k-column block (k - 1 for k >= 2, none for k = 1) and the bytes of its
+ * workspace, in 64 bits.  KRCN_ERR_INVALID: k outside
+ * [1, KRCN_SSCN_TRIDIAG_MAX], a null pointer. */
+krcn_status krcn_dense_tridiag_geometry(int k, int64_t* launches_host, int64_t* workspace_bytes_host);
+
+/* SYNCHRONOUS.  The reduction alone, for a symmetric k x k H (HOST, row-major;
+ * only the upper triangle, column >= row, is read, as by krcn_cubic_dense) and
+ * g (k HOST doubles), 1 <= k <= KRCN_SSCN_TRIDIAG_MAX.  alphas_host (k): T's
+ * diagonal.  betas_host (k): betas[0] = b_0, the signed ||g||; betas[1..k) T's
+ * off-diagonal.  Q_host, if not NULL (k x k, row-major): Q, formed by
+ * back-transforming the k unit vectors (a test path, one workgroup a column).
+ * H = Q T Q^T and g = b_0 Q e1.  Argument errors (null handle or pointer other
+ * than Q_host, k outside the range) are KRCN_ERR_INVALID before any HIP call.
+ * Replaces nothing of the reference by itself: it is the factorisation that
+ * krcn_cubic_dense_tridiag puts in place of the per-lam solves of
+ * cubic_solver_root, cubic.py:60-62 (func), :64-67 (grad) and :72. */
+krcn_status krcn_dense_tridiag(krcn_csr* h, int k, const double* H_host, const double* g_host,
+                               double* alphas_host, double* betas_host, double* Q_host, void* stream);
+
+/* SYNCHRONOUS.  krcn_cubic_dense's contract and result record for
+ * 1 <= k <= KRCN_SSCN_TRIDIAG_MAX by the route above: one reduction, then
+ * krcn_cubic_tridiag's kernel on (alphas, betas[1..k), gnorm = b_0) — the same
+ * scalar Newton loop, one LDL^T of T + lam I per lam — and the back-transform
+ * s = Q s_T (reflectors applied last to first).  The solver statuses keep their
+ * meaning: a non-positive or non-finite pivot of the LDL^T is solver_status 1
+ * (the host's LinAlgError), 2 phi' = 0, 3 it_max reached; s_host is zeroed on 1
+ * and 2.  Argument errors (null handle or pointer, k outside the range,
+ * it_max < 1) are KRCN_ERR_INVALID before any HIP call.
+ * Replaces cubic_solver_root, cubic.py:40-75 (its dense branch :49-52, :56-58
+ * and, for a sparse H of 500 or more columns, its spsolve branch :53-55), as
+ * SSCN calls it
+ * (cubic.py:373-374, :386-387). */
+krcn_status krcn_cubic_dense_tridiag(krcn_csr* h, int k, const double* H_host, const double* g_host, double M,
+                                     double r0, double eps, int it_max, double* s_host,
+                                     krcn_crn_info* info_host, void* stream);
+
+/* SYNCHRONOUS.  krcn_sscn_step's signature and contract with
+ * 1 <= k <= KRCN_SSCN_TRIDIAG_MAX.  The chain: Ax = X x if Ax is NULL, the
+ * coordinate gradient and Hessian block, the reduction (once per step, before
+ * the first trial, whatever the number of trials), x_new = x, the chain's begin
+ * with M = max(reg_coef * ls_beta, DBL_EPSILON), gnorm = b_0 and m_eff = k; then
+ * the trials, each [tridiagonal solve -> back-transform (writes s and
+ * x_new[c_a] = x[c_a] + s_a) -> coordinate update of Ax -> loss and norm
+ * partials -> judge], in krcn_sscn_step's batches over the same chain state.
+ * info_host as krcn_sscn_step's; dx_norm is ||s_T|| (= ||s||).  The same
+ * refusals with the same position-naming messages: an index outside [0, d), a
+ * repeated index, k outside the range (KRCN_ERR_INVALID before any launch);
+ * sharded handles get KRCN_ERR_UNSUPPORTED.  Workspace: the coordinate
+ * workspace, the step workspace of krcn_crn_step and the reduction's; a second
+ * step with the same k allocates nothing.  Builds pass plans only when Ax is
+ * NULL, before any scratch buffer is read.
+ * Replaces the body of SSCN.step, cubic.py:352-398. */
+krcn_status krcn_sscn_step_tridiag(krcn_csr* h, int k, const int32_t* cols_host, const void* x, const void* b,
+                                   const void* Ax, double value, double l2, double reg_coef, double ls_beta,
+                                   double r0, double solver_eps, int solver_it_max, int max_trials, void* x_new,
+                                   void* Ax_new, krcn_crn_info* info_host, void* stream);
+
 /* ---- the full-space cubic subproblem on the device: Newton over CG -------- */
 /* Result record of krcn_cubic_cg. */
 typedef struct {

@@ -353,6 +353,8 @@ struct krcn_csr {
   int coord_window = 0;       // krcn_csr_set_coord_window (0: auto)
   char* sscn_ws = nullptr;    // krcn_sscn_step: the selection in both orders, its permutation and the
                               //   coordinate gradient (krcn_sscn.hip; a fixed block, allocated by the first step)
+  double* sytd_ws = nullptr;  // the tridiagonal reduction's workspace for blocks of up to sytd_k columns
+  int sytd_k = 0;             //   (krcn_sytd.hip; allocated by the first call that needs it, grown when k grows)
   void* blk_u = nullptr;      // krcn_hvp_block: its (n, blk_k) intermediate (krcn_block.hip; grown when k grows)
   int blk_k = 0;
   int* blk_long[2] = {};      // block products: rows of X / X^T above KRCN_BLOCK_LONG_ROW, listed at the

@@ -31,6 +31,7 @@ KRCN_SPACE_N, KRCN_SPACE_D = 0, 1
 KRCN_COORD_MAX = 1024
 KRCN_BLOCK_MAX, KRCN_BLOCK_LONG_ROW = 16, 512
 KRCN_SSCN_MAX = 128
+KRCN_SSCN_TRIDIAG_MAX = 1024
 
 _STATUS_NAMES = {1: "KRCN_ERR_INVALID", 2: "KRCN_ERR_HIP", 3: "KRCN_ERR_RCCL",
                  4: "KRCN_ERR_UNSUPPORTED"}
@@ -139,6 +140,11 @@ SIGNATURES = {
     "krcn_cubic_dense": [_vp, _i, _dp, _dp, _d, _d, _d, _i, _dp, ctypes.POINTER(CrnInfo), _vp],
     "krcn_sscn_step": [_vp, _i, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _d, _d, _i, _i, _vp, _vp,
                        ctypes.POINTER(CrnInfo), _vp],
+    "krcn_dense_tridiag_geometry": [_i, ctypes.POINTER(_i64), ctypes.POINTER(_i64)],
+    "krcn_dense_tridiag": [_vp, _i, _dp, _dp, _dp, _dp, _dp, _vp],
+    "krcn_cubic_dense_tridiag": [_vp, _i, _dp, _dp, _d, _d, _d, _i, _dp, ctypes.POINTER(CrnInfo), _vp],
+    "krcn_sscn_step_tridiag": [_vp, _i, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _d, _d, _i, _i, _vp, _vp,
+                               ctypes.POINTER(CrnInfo), _vp],
     "krcn_cubic_cg": [_vp, _vp, _vp, _d, _d, _d, _d, _i, _d, _i, _vp, ctypes.POINTER(CubicCgInfo), _vp],
     "krcn_hessian_gram": [_vp, _vp, _d, _vp, _vp],
     "krcn_csr_set_gram_split": [_vp, _i],

@@ -629,8 +629,55 @@ class DeviceCSR:
              _stream(self.device))
         return s[:k], info
 
+    @staticmethod
+    def dense_tridiag_geometry(k):
+        """(column launches, workspace bytes) of the tridiagonal reduction of a
+        k-column block (krcn_dense_tridiag_geometry; host arithmetic only)."""
+        launches, ws = ctypes.c_int64(0), ctypes.c_int64(0)
+        call("krcn_dense_tridiag_geometry", int(k), ctypes.byref(launches), ctypes.byref(ws))
+        return launches.value, ws.value
+
+    @staticmethod
+    def _dense_block(H, g):
+        Hd = np.ascontiguousarray(H.toarray() if hasattr(H, "toarray") else H, dtype=np.float64)
+        gd = np.ascontiguousarray(g, dtype=np.float64).reshape(-1)
+        k = len(gd)
+        if Hd.shape != (k, k):
+            raise ValueError(f"H must be ({k}, {k}), got {Hd.shape}")
+        return Hd, gd, k
+
+    def dense_tridiag(self, H, g, want_q=False):
+        """The Householder reduction behind `cubic_dense_tridiag` alone
+        (krcn_dense_tridiag), 1 <= k <= KRCN_SSCN_TRIDIAG_MAX: H = Q T Q^T with
+        T = tridiag(betas[1:], alphas, betas[1:]) and g = betas[0] Q e1
+        (betas[0] is the signed ||g||).  Only the upper triangle of H is read.
+        Returns (alphas, betas, Q); Q is None unless want_q (a test path)."""
+        Hd, gd, k = self._dense_block(H, g)
+        n = max(k, 1)
+        al = np.full(n, np.nan)
+        be = np.full(n, np.nan)
+        Q = np.full((n, n), np.nan) if want_q else None
+        call("krcn_dense_tridiag", self._h, k, Hd.ctypes.data_as(_lib._dp), gd.ctypes.data_as(_lib._dp),
+             al.ctypes.data_as(_lib._dp), be.ctypes.data_as(_lib._dp),
+             Q.ctypes.data_as(_lib._dp) if want_q else None, _stream(self.device))
+        return al[:k], be[:k], (Q[:k, :k] if want_q else None)
+
+    def cubic_dense_tridiag(self, H, g, M, r0=0.1, eps=1e-8, it_max=100):
+        """`cubic_dense` for 1 <= k <= KRCN_SSCN_TRIDIAG_MAX over one
+        tridiagonal reduction of H (krcn_cubic_dense_tridiag): the reduction,
+        the tridiagonal subproblem of `cubic_tridiag`, and s = Q s_T.  Returns
+        (s, info) as `cubic_dense`."""
+        Hd, gd, k = self._dense_block(H, g)
+        s = np.full(max(k, 1), np.nan)
+        info = _lib.CrnInfo()
+        call("krcn_cubic_dense_tridiag", self._h, k, Hd.ctypes.data_as(_lib._dp), gd.ctypes.data_as(_lib._dp),
+             float(M), float(r0), float(eps), int(it_max), s.ctypes.data_as(_lib._dp), ctypes.byref(info),
+             _stream(self.device))
+        return s[:k], info
+
     def sscn_step(self, cols, x, b, value, reg_coef, Ax=None, l2=0.0, ls_beta=0.5, r0=0.1,
-                  solver_eps=float(np.finfo(float).eps), solver_it_max=100, max_trials=20, x_new=None, Ax_new=None):
+                  solver_eps=float(np.finfo(float).eps), solver_it_max=100, max_trials=20, x_new=None, Ax_new=None,
+                  subproblem="cholesky"):
         """One SSCN step from x with f(x) = value over the distinct columns
         `cols` behind one library call (krcn_sscn_step): coordinate gradient
         and Hessian block, then the backtracking line search with the dense
@@ -638,7 +685,12 @@ class DeviceCSR:
         on the device.  Ax is X x when the caller has it.  Returns (x_new,
         Ax_new, info): the iterate the step keeps, its product with X, and a
         _lib.CrnInfo (accepted, trials, solver_it, solver_status, reg_coef,
-        lam, model_decrease, value_new, dx_norm = ||s||)."""
+        lam, model_decrease, value_new, dx_norm = ||s||).
+        subproblem: "cholesky" (krcn_sscn_step, up to KRCN_SSCN_MAX columns: a
+        Cholesky factorisation per lam) or "tridiag" (krcn_sscn_step_tridiag, up
+        to KRCN_SSCN_TRIDIAG_MAX: one tridiagonal reduction per step)."""
+        if subproblem not in ("cholesky", "tridiag"):
+            raise ValueError(f'subproblem must be "cholesky" or "tridiag", got {subproblem!r}')
         c, cp = self._selection(cols)
         self._check(x, self.d, "x")
         self._check(b, self.n, "b")
@@ -647,7 +699,7 @@ class DeviceCSR:
         x_new = self.empty_d() if x_new is None else self._check(x_new, self.d, "x_new")
         Ax_new = self.empty_n() if Ax_new is None else self._check(Ax_new, self.n, "Ax_new")
         info = _lib.CrnInfo()
-        call("krcn_sscn_step", self._h, len(c), cp, _ptr(x), _ptr(b), _ptr(Ax), float(value), float(l2),
+        call("krcn_sscn_step" if subproblem == "cholesky" else "krcn_sscn_step_tridiag", self._h, len(c), cp, _ptr(x), _ptr(b), _ptr(Ax), float(value), float(l2),
              float(reg_coef), float(ls_beta), float(r0), float(solver_eps), int(solver_it_max), int(max_trials),
              _ptr(x_new), _ptr(Ax_new), ctypes.byref(info), _stream(self.device))
         return x_new, Ax_new, info

@@ -654,19 +654,34 @@ class SSCN(Optimizer):
     after 20 rejected trials and keeps the last one, as Cubic_Krylov_LS does:
     that step warns (RuntimeWarning) and is counted in `capped_steps`.
     `last_trials` holds the backtracking trials of the last step on both
-    paths."""
+    paths.
+
+    subproblem="tridiag" (device_step=True only; default "cholesky") runs the
+    device step through krcn_sscn_step_tridiag: the block is reduced once per
+    step to tridiagonal form and every trial solves the tridiagonal subproblem,
+    which lifts the cap on subspace_dim to KRCN_SSCN_TRIDIAG_MAX = 1024.  The
+    differences of the device step above carry over unchanged."""
 
     def __init__(self, reg_coef=None, subspace_dim=100, solver_eps=1e-8, beta=0.5, *args, device_step=False,
-                 **kwargs):
+                 subproblem="cholesky", **kwargs):
         super().__init__(*args, **kwargs)
+        if subproblem not in ("cholesky", "tridiag"):
+            raise ValueError(f'subproblem must be "cholesky" or "tridiag", got {subproblem!r}')
+        if subproblem == "tridiag" and not device_step:
+            raise ValueError('subproblem="tridiag" is the device step\'s: it needs device_step=True')
         if device_step:
             from krcn import _lib
             if getattr(self.loss, "shard", None) is not None:
                 raise NotImplementedError("device_step=True is implemented for unsharded problems")
-            if not 1 <= int(subspace_dim) <= _lib.KRCN_SSCN_MAX:
+            if subproblem == "tridiag":
+                if not 1 <= int(subspace_dim) <= _lib.KRCN_SSCN_TRIDIAG_MAX:
+                    raise ValueError(f'device_step=True with subproblem="tridiag" needs 1 <= subspace_dim <= '
+                                     f"{_lib.KRCN_SSCN_TRIDIAG_MAX}, got {subspace_dim}")
+            elif not 1 <= int(subspace_dim) <= _lib.KRCN_SSCN_MAX:
                 raise ValueError(f"device_step=True needs 1 <= subspace_dim <= {_lib.KRCN_SSCN_MAX}, "
                                  f"got {subspace_dim}")
         self.device_step = bool(device_step)
+        self.subproblem = subproblem
         self.last_trials = 0
         self.capped_steps = 0       # device steps that ended at the trial cap without an accepted trial
         self.reg_coef = reg_coef
@@ -733,7 +748,8 @@ class SSCN(Optimizer):
         I = self.rng.choice(self.dim, size=self.subspace_dim, replace=False)
         x_new, Ax_new, info = X.sscn_step(
             I, self.x, loss._b_dev, self.value, self.reg_coef, Ax=loss._device_Ax(self.x), l2=float(loss.l2),
-            ls_beta=self.beta, r0=self.r0, solver_eps=np.finfo(float).eps, max_trials=20)
+            ls_beta=self.beta, r0=self.r0, solver_eps=np.finfo(float).eps, max_trials=20,
+            subproblem=self.subproblem)
         if info.solver_status == 1:
             raise la.LinAlgError("H + lam I is not positive definite")
         if info.solver_status == 2:
