@@ -2,10 +2,10 @@
 // (krcn_cubic_tridiag) and one Krylov-CRN step behind one call (krcn_crn_step):
 // gradient, weights, the Lanczos recurrence, then a chain of guarded
 // backtracking trials whose accept / reject decision is taken on the device
-// (krcn_cubic.hpp).  Replaces the host loop of Cubic_Krylov_LS.step,
-// optimizer/cubic.py:239-270 (reference cubic.py:265-309).
-#include "krcn_cubic.hpp"
-#include "krcn_internal.hpp"
+// (krcn_cubic.hpp; the chain's host side is krcn_crn_chain.hpp's).  Replaces
+// the host loop of Cubic_Krylov_LS.step, optimizer/cubic.py:239-270 (reference
+// cubic.py:265-309).
+#include "krcn_crn_chain.hpp"
 
 static_assert(kCubicMaxM == kLzMaxM, "the subproblem kernel's LDS vectors hold the largest Lanczos m");
 
@@ -13,16 +13,13 @@ namespace {
 
 constexpr size_t kCrnStateDoubles = sizeof(CrnState) / sizeof(double);
 
-struct CrnWs {
-  CrnState* st;
+struct CrnWs : CrnRec {
   double *al, *be, *s;
-  CrnState* res;   // the mapped host record, by its device address
 };
 
 CrnWs crn_ws(const krcn_csr* h) {
   double* v = h->crn_ws + kCrnStateDoubles;
-  return CrnWs{reinterpret_cast<CrnState*>(h->crn_ws), v, v + kLzMaxM, v + 2 * size_t(kLzMaxM),
-               reinterpret_cast<CrnState*>(h->crn_res_dev)};
+  return CrnWs{crn_rec(h), v, v + kLzMaxM, v + 2 * size_t(kLzMaxM)};
 }
 
 struct StepArgs {
@@ -33,7 +30,7 @@ struct StepArgs {
 template <typename T>
 krcn_status crn_step_impl(krcn_csr* h, const T* x, const T* b, const T* Ax, const StepArgs& a, T* V, T* x_new,
                           T* Ax_new, double* alphas_host, double* betas_host, krcn_crn_info* info, hipStream_t s) {
-  const int64_t n = h->n, d = h->d;
+  const int64_t d = h->d;
   CHK(plans_for_compute(h));   // before any scratch pointer is read: a plan build may move them
   CHK(ensure_crn_ws(h));
   const CrnWs ws = crn_ws(h);
@@ -56,7 +53,7 @@ krcn_status crn_step_impl(krcn_csr* h, const T* x, const T* b, const T* Ax, cons
                      a.reg_coef * a.ls_beta, ws.st, ws.al, ws.be);
   LAUNCHCHK();
   const LanczosState* guard = reinterpret_cast<const LanczosState*>(ws.st);
-  const int Pn = vec_grid(n), Pd = vec_grid(d);
+  const int Pd = vec_grid(d);
   auto trial = [&]() -> krcn_status {
     hipLaunchKernelGGL(k_cubic_tridiag, dim3(1), dim3(kNT), 0, s, ws.st, static_cast<const double*>(ws.al),
                        static_cast<const double*>(ws.be), ws.s, a.r0, a.solver_eps, a.solver_it_max, ws.res);
@@ -66,48 +63,27 @@ krcn_status crn_step_impl(krcn_csr* h, const T* x, const T* b, const T* Ax, cons
     LAUNCHCHK();
     const SrcGuard<T> src{x_new, guard, 0};
     CHK(run_pass<T>(h->p1, src, src, EpiStore<T>{Ax_new}, nullptr, nullptr, s));
-    hipLaunchKernelGGL((k_loss_terms_guard<T>), dim3(Pn), dim3(kNT), 0, s, n, static_cast<const T*>(Ax_new), b, h->pa,
-                       static_cast<const CrnState*>(ws.st));
-    LAUNCHCHK();
-    if (a.l2 != 0.0) {
-      hipLaunchKernelGGL((k_sqnorm_guard<T>), dim3(Pd), dim3(kNT), 0, s, d, static_cast<const T*>(x_new),
-                         static_cast<const T*>(nullptr), h->pb, static_cast<const CrnState*>(ws.st), 0);
-      LAUNCHCHK();
-    }
-    hipLaunchKernelGGL(k_crn_judge, dim3(1), dim3(kNT), 0, s, static_cast<const double*>(h->pa), Pn,
-                       static_cast<const double*>(h->pb), Pd, double(h->n_global), a.l2, a.value, a.ls_beta,
-                       a.max_trials, ws.st, ws.res);
-    LAUNCHCHK();
-    return KRCN_OK;
+    return crn_judge_trial<T>(h, ws, Ax_new, b, x_new, double(h->n_global), a.l2, a.value, a.ls_beta, a.max_trials,
+                              s);
   };
-  CrnState st{};
-  const int total = a.max_trials + 1;   // the trial after max_trials rejections ends the chain itself
-  for (int enq = 0; enq < total && !st.done;) {
-    const int batch = std::min(enq == 0 ? kCrnFirstBatch : kCrnBatch, total - enq);
-    for (int k = 0; k < batch; ++k) CHK(trial());
-    enq += batch;
-    // the step length, in the submission of the batch that ends the chain (others skip it)
+  // the step length, in the submission of the batch that ends the chain (others skip it)
+  auto step_length = [&]() -> krcn_status {
     hipLaunchKernelGGL((k_sqnorm_guard<T>), dim3(Pd), dim3(kNT), 0, s, d, static_cast<const T*>(x_new), x, h->pb,
                        static_cast<const CrnState*>(ws.st), 1);
     LAUNCHCHK();
     hipLaunchKernelGGL(k_crn_dx_finish, dim3(1), dim3(kNT), 0, s, static_cast<const double*>(h->pb), Pd, ws.st,
                        ws.res);
     LAUNCHCHK();
-    HIPCHK(hipStreamSynchronize(s));
-    std::memcpy(&st, h->crn_res, sizeof(CrnState));
-  }
-  if (!st.done) return fail(KRCN_ERR_HIP, "krcn_crn_step: the trial chain did not end after %d trials", total);
+    return KRCN_OK;
+  };
+  CrnState st;
+  CHK(crn_run_chain(h, "krcn_crn_step", a.max_trials, s, trial, step_length, &st));
   double be1 = 0.0;   // (m = 1 has no betas)
   std::vector<double> al_tmp;
   if (!alphas_host || !betas_host) al_tmp.resize(2 * size_t(a.m));
   lanczos_results(h, a.m, alphas_host ? alphas_host : al_tmp.data(),
                   betas_host ? betas_host : (a.m > 1 ? al_tmp.data() + a.m : &be1), &info->lanczos);
-  crn_solver_fields(st, info);
-  info->accepted = st.accepted;
-  info->trials = st.trials;
-  info->value_new = st.value_new;
-  const bool failed = st.solver_status == kCubicNotPd || st.solver_status == kCubicDerZero;
-  info->dx_norm = failed ? 0.0 : std::sqrt(st.dx2);
+  crn_step_fields(st, info);
   return KRCN_OK;
 }
 
@@ -146,14 +122,7 @@ extern "C" krcn_status krcn_cubic_tridiag(krcn_csr* h, int m, const double* alph
     hipLaunchKernelGGL(k_cubic_tridiag, dim3(1), dim3(kNT), 0, s, ws.st, static_cast<const double*>(ws.al),
                        static_cast<const double*>(ws.be), ws.s, r0, eps, it_max, ws.res);
     LAUNCHCHK();
-    HIPCHK(hipMemcpyAsync(h->hostbuf, ws.s, size_t(m) * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    CrnState st;
-    std::memcpy(&st, h->crn_res, sizeof(CrnState));
-    crn_solver_fields(st, info_host);
-    const bool solved = st.solver_status == kCubicOk || st.solver_status == kCubicItMax;
-    for (int i = 0; i < m; ++i) s_host[i] = solved ? h->hostbuf[i] : 0.0;
-    return KRCN_OK;
+    return crn_read_solve(h, ws.s, m, s_host, info_host, s);
   } catch (...) {
     return fail(KRCN_ERR_INVALID, "krcn_cubic_tridiag: unexpected C++ exception");
   }

@@ -7,7 +7,7 @@
 // judge kernel of the trial that ends the line search (or by the subproblem
 // kernel when its solve fails), and every later launch of the chain returns at
 // once, so the host enqueues trials in batches and reads the state once per
-// batch.  The arithmetic of the subproblem is fp64 whatever the handle's dtype.
+// batch (krcn_crn_chain.hpp: the host side of every such chain).  The arithmetic of the subproblem is fp64 whatever the handle's dtype.
 #pragma once
 #include <cstddef>
 
@@ -40,21 +40,12 @@ struct CrnState {
 static_assert(offsetof(CrnState, done) == offsetof(LanczosState, done), "SrcGuard reads done");
 static_assert(sizeof(CrnState) % sizeof(double) == 0, "the state heads a block of doubles");
 
-// Trials per submission of a chain (krcn_crn_step, krcn_sscn_step): the first
-// holds trials 0 and 1, every later one kCrnBatch (a guarded
-// trial that finds done set costs its launches only, a host round trip costs a
-// synchronisation).
+// Trials per submission of a chain (crn_run_chain, krcn_crn_chain.hpp): the
+// first holds trials 0 and 1, every later one kCrnBatch (a
+// guarded trial that finds done set costs its launches only, a host round trip
+// costs a synchronisation).
 constexpr int kCrnFirstBatch = 2;
 constexpr int kCrnBatch = 4;
-
-// The solver fields of a chain's record, as the host reads them back.
-inline void crn_solver_fields(const CrnState& st, krcn_crn_info* info) {
-  info->solver_it = st.solver_it;
-  info->solver_status = st.solver_status;
-  info->reg_coef = st.M;
-  info->lam = st.lam;
-  info->model_decrease = st.model_decrease;
-}
 
 // Start of a chain.  lz != nullptr: the block k_lz_final packed (state,
 // alphas[0..m), betas[0..m-1)) becomes the subproblem's input, with the

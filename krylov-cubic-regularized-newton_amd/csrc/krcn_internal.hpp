@@ -10,8 +10,12 @@
 //   krcn_block.hip       block products: k vectors per pass over the matrix (X V, X^T U / n, the block HVP)
 //   krcn_lanczos_block.hip  the batched Lanczos: k recurrences in lockstep over the block HVP (krcn_blz.hpp;
 //                        its per-column state rule, krcn_blz_state.hpp, is host-only like the three below)
-//   krcn_crn.hip         the device cubic subproblem and the one-call Krylov-CRN step (krcn_cubic.hpp)
-//   krcn_sscn.hip        the dense cubic subproblem and the one-call SSCN step (krcn_cubic_dense.hpp)
+//   krcn_crn.hip         the device cubic subproblem and the one-call Krylov-CRN step (krcn_cubic.hpp; the host
+//                        side of its trial chain, krcn_crn_chain.hpp, is also the SSCN steps')
+//   krcn_sscn.hip        the dense cubic subproblem and the Cholesky route of the one-call SSCN step
+//                        (krcn_cubic_dense.hpp; the step and its entry checks, krcn_sscn_step.hpp, over the
+//                        host-only selection rule, krcn_sscn_sel.hpp)
+//   krcn_sytd.hip        the tridiagonal reduction and the tridiagonal route of the same step (krcn_sytd.hpp)
 //   krcn_cubic_cg.hip    the full-space cubic subproblem, Newton over CG in one call (krcn_cgn.hpp; its
 //                        state rule, krcn_cgn_state.hpp, is host-only like the three below)
 //   krcn_gram.hip        the dense Hessian as a Gram product over the dense X^T image, fp64 MFMA (krcn_gram.hpp;

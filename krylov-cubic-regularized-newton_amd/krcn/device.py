@@ -617,11 +617,7 @@ class DeviceCSR:
         (krcn_cubic_dense; what optimizer.cubic.cubic_solver_root computes on
         the host).  Only the upper triangle of H is read.  Returns (s, info) as
         `cubic_tridiag`: status 1 means H + lam I was not positive definite."""
-        Hd = np.ascontiguousarray(H.toarray() if hasattr(H, "toarray") else H, dtype=np.float64)
-        gd = np.ascontiguousarray(g, dtype=np.float64).reshape(-1)
-        k = len(gd)
-        if Hd.shape != (k, k):
-            raise ValueError(f"H must be ({k}, {k}), got {Hd.shape}")
+        Hd, gd, k = self._dense_block(H, g)
         s = np.zeros(max(k, 1), dtype=np.float64)
         info = _lib.CrnInfo()
         call("krcn_cubic_dense", self._h, k, Hd.ctypes.data_as(_lib._dp), gd.ctypes.data_as(_lib._dp), float(M),
@@ -699,9 +695,10 @@ class DeviceCSR:
         x_new = self.empty_d() if x_new is None else self._check(x_new, self.d, "x_new")
         Ax_new = self.empty_n() if Ax_new is None else self._check(Ax_new, self.n, "Ax_new")
         info = _lib.CrnInfo()
-        call("krcn_sscn_step" if subproblem == "cholesky" else "krcn_sscn_step_tridiag", self._h, len(c), cp, _ptr(x), _ptr(b), _ptr(Ax), float(value), float(l2),
-             float(reg_coef), float(ls_beta), float(r0), float(solver_eps), int(solver_it_max), int(max_trials),
-             _ptr(x_new), _ptr(Ax_new), ctypes.byref(info), _stream(self.device))
+        fn = "krcn_sscn_step" if subproblem == "cholesky" else "krcn_sscn_step_tridiag"
+        call(fn, self._h, len(c), cp, _ptr(x), _ptr(b), _ptr(Ax), float(value), float(l2), float(reg_coef),
+             float(ls_beta), float(r0), float(solver_eps), int(solver_it_max), int(max_trials), _ptr(x_new),
+             _ptr(Ax_new), ctypes.byref(info), _stream(self.device))
         return x_new, Ax_new, info
 
     # -- the full-space cubic subproblem on the device --------------------------
